@@ -19,6 +19,13 @@ delivered / wall time.  `timing.submit_to_done_ms` is one frame's latency.  Side
 time the FP64 [Vec3] framebuffer delivered synchronously (`fp64_path`, rt_render) and the
 device-only launch (`device_only`).
 
+A plain run does only what `value` needs: scene, warmup, the K timed steps, the line.  `--full`
+adds everything measured or checked after the timed steps (single-frame kernel time and the
+roofline, side paths, CPU baseline, the gathered frame's completeness and hash, NUMA page
+placement, the per-rank device-only loop for N > 1); without it those fields are null.
+`--dump-outputs DIR` writes the last timed step's delivered frame and ray counts as .npy files
+(the scene is seeded, so two builds can be compared output for output).
+
 N GPUs: one process per GPU (torchrun; `python bench.py --gpus N` starts torchrun itself
 before anything touches a GPU).  Default for N>1 is configs[3] "C4", STRONG scaling: ONE
 C3 frame per step, 8-row chunk c rendered by rank c mod N (Object+Extension.swift:75-82),
@@ -95,14 +102,49 @@ def parse():
                         "library's own streams; 0 = HIP's default)")
     p.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                    help="render option for the run (rt_scene_set_option, INTEGRATION.md table); repeatable")
-    p.add_argument("--no-cpu-baseline", action="store_true")
-    p.add_argument("--no-side-paths", action="store_true", help="skip the fp64 / device-only side measurements")
+    p.add_argument("--full", action="store_true",
+                   help="after the timed steps also measure and check everything beside the headline figure: the "
+                        "render kernel's own duration and the roofline, the fp64 / device-only side paths, the CPU "
+                        "baseline, the gathered frame's completeness and hash, NUMA page placement and (N > 1) the "
+                        "per-rank device-only loop.  Without it the run sets up, warms up, times the steps and "
+                        "prints the line, with those fields null")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps write what the last timed step delivered as DIR/<name>.npy "
+                        "(rank 0): rgba8 = the RGBA8 frame as float32 (a fixed, seeded sample of its pixels with "
+                        "their indices in rgba8_pixels when the frame exceeds the size cap), ray_counts = that "
+                        "frame's ray counters as float64")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    p.add_argument("--no-side-paths", action="store_true",
+                   help="with --full: skip the fp64 / device-only side measurements")
     p.add_argument("--cpu-threads", type=int, default=0, help="0 = the CPU share (OMP_NUM_THREADS / affinity)")
     p.add_argument("--cpu-frames", type=int, default=3)
-    p.add_argument("--cache", default=os.path.join(ROOT, "scenes_cache"))
+    p.add_argument("--cache", default=None,
+                   help="folder for the generated scene PLYs; default: scenes_cache/ next to this file, or, where "
+                        "that cannot be written, a per-user cache or temporary folder (scene_cache_dir)")
     p.add_argument("--profile-json", default="auto",
                    help="PMC summary (tools/pmc_roofline.py); auto = profiles/roofline_<config>.json")
     return p.parse_args()
+
+
+def scene_cache_dir(candidates=None):
+    """The first folder the generated scene PLYs can be written to: scenes_cache/ in the source
+    tree, else the user's cache, else the temporary folder (the tree may be read-only for the
+    user who runs the bench).  The same for every rank of a run: no process id in the name."""
+    import tempfile
+    if candidates is None:
+        home_cache = os.environ.get("XDG_CACHE_HOME") or os.path.join(os.path.expanduser("~"), ".cache")
+        candidates = [os.path.join(ROOT, "scenes_cache"),
+                      os.path.join(home_cache, "myraytracer_amd", "scenes"),
+                      os.path.join(tempfile.gettempdir(), f"myraytracer_amd_scenes_{os.getuid()}")]
+    for d in candidates:
+        try:
+            os.makedirs(d, exist_ok=True)
+        except OSError:
+            continue
+        if os.access(d, os.W_OK | os.X_OK):
+            return d
+    raise SystemExit("bench.py: no writable folder for the scene files (tried " + ", ".join(candidates) +
+                     "); pass --cache DIR")
 
 
 def log(*a):
@@ -284,6 +326,8 @@ def main():
     from myraytracer_amd import scenes
 
     t0 = time.time()
+    if args.cache is None:
+        args.cache = scene_cache_dir()
     if args.config == "c3":
         scene = scenes.scene_c3(path_dir=args.cache)
         workload = "C3: ~1.02M-tri PLY (heightfield+24 icospheres), 1920x1080, 1 spp, 1 point light, shadows"
@@ -402,7 +446,9 @@ def main():
     scratch_after_warmup = int(eng.info().scratch_bytes)
     # where this rank's rows of the delivered frames live (pages per NUMA node; the shared frames
     # for N > 1, this rank's own page-locked frames for N = 1)
-    if strong and world > 1 and not staged:
+    if not args.full:
+        pass
+    elif strong and world > 1 and not staged:
         pg = collections.Counter()
         row_b = W * 4
         for sf in shared:
@@ -430,26 +476,31 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t_begin = time.perf_counter()
-    run(args.steps, per)
+    st_last = run(args.steps, per)
     torch.cuda.synchronize()
     t_elapsed = time.perf_counter() - t_begin
     calls = [b for _, b in per]
     if world > 1:
         dist.barrier()
+    if args.dump_outputs and rank == 0:
+        # before anything below renders into the framebuffers again
+        dump_outputs(args.dump_outputs, gathered[(args.steps - 1) % Q], st_last)
     # the render kernel's own launch duration (roofline): HIP events around it, one frame at a
     # time (with frames in flight the event span also covers the overlapped neighbours)
-    one = eng.frame_renderer(0, first, step, rgb=None, rgba=fbs[0], frame_layout=True)
-    sync = []
-    for _ in range(max(5, min(args.steps, 20))):
-        s_ = one()
-        sync.append((s_.kernel_ms, s_.milliseconds))
-    kernel_ms = statistics.mean(a for a, _ in sync)
-    sync_ms = statistics.mean(b for _, b in sync)
+    kernel_ms = sync_ms = None
+    if args.full:
+        one = eng.frame_renderer(0, first, step, rgb=None, rgba=fbs[0], frame_layout=True)
+        sync = []
+        for _ in range(max(5, min(args.steps, 20))):
+            s_ = one()
+            sync.append((s_.kernel_ms, s_.milliseconds))
+        kernel_ms = statistics.mean(a for a, _ in sync)
+        sync_ms = statistics.mean(b for _, b in sync)
 
     t_max = t_elapsed
     tot = np.array([rays_rank, rays_primary + shadow_cast, shadow_cast, shadow_traced], dtype=np.float64) * args.steps
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         # the same pipelined loop with the image left in HBM (option submit_dma = 2: rows rendered
         # into device staging, not delivered): each rank's device-only time per frame, so the first
         # multi-GPU line tells compute scaling from host-gather bandwidth
@@ -492,9 +543,10 @@ def main():
         rr = torch.tensor(tot)
         dist.all_reduce(rr, op=dist.ReduceOp.SUM)
         tot = rr.numpy()
-        km = torch.tensor([kernel_ms], dtype=torch.float64)
-        dist.all_reduce(km, op=dist.ReduceOp.MAX)
-        kernel_ms = float(km.item())
+        if args.full:
+            km = torch.tensor([kernel_ms], dtype=torch.float64)
+            dist.all_reduce(km, op=dist.ReduceOp.MAX)
+            kernel_ms = float(km.item())
     value = tot[0] / t_max / 1e6
     ms_per_step = t_max * 1e3 / args.steps
 
@@ -503,7 +555,7 @@ def main():
     if world > 1:
         dist.barrier()
     gather = None
-    if rank == 0:
+    if rank == 0 and args.full:
         fb = gathered[(args.steps - 1) % Q]                  # the last frame delivered
         gather = {"rows_complete": bool(all(np.all(f_[:, :, 3] == 255) for f_ in gathered)),
                   "rgba8_sha256": hashlib.sha256(np.ascontiguousarray(fb).tobytes()).hexdigest(),
@@ -511,15 +563,17 @@ def main():
                   "mode": args.gather if (strong and world > 1) else "single"}
 
     # ---- roofline (profiles/roofline_<config>.json: PMC passes of this build, tools/pmc_roofline.py)
-    roofline = roofline_fields(args, eng, local, first, step, rows, W, kernel_ms, rays_rank, world)
+    roofline = None
+    if args.full:
+        roofline = roofline_fields(args, eng, local, first, step, rows, W, kernel_ms, rays_rank, world)
 
     # ---- side paths on this rank's share: FP64 framebuffer delivery, device-only launch
     side = None
-    if not args.no_side_paths:
+    if args.full and not args.no_side_paths:
         side = side_paths(eng, first, step, rows, W, H, rays_rank, args)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         try:
             cpu = cpu_baseline(scene, H, args)
         except Exception as e:  # pragma: no cover
@@ -533,7 +587,7 @@ def main():
             "metric": "Mrays/s (primary+shadow), 1920x1080 / 1M-tri PLY, at 1/2/4/8 MI355X",
             "value": round(float(value), 2), "unit": "Mrays/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "strong" if strong else "weak", "vs_baseline": None,
+            "scaling": "strong" if strong else "weak", "vs_baseline": None, "full": bool(args.full),
             "dtype": "f64", "data": "synthetic (seeded scene generator; no bunny/assets offline)",
             "config": {"workload": workload, "width": W, "height": H, "spp": max(1, cam.num_samples),
                        "triangles": int(info.triangles),
@@ -554,17 +608,19 @@ def main():
                      "rewalked_what": "closest-hit rays of rank 0's share that the four-wide walk handed to the "
                                       "reference-order walk (two candidates at the final t, wide.h)"},
             "per_rank": per_rank,
-            "numa": numa if world == 1 else {"placement": args.numa_placement, "per_rank": "per_rank.numa"},
+            "numa": (None if not args.full else numa if world == 1 else
+                     {"placement": args.numa_placement, "per_rank": "per_rank.numa"}),
             "scene": {"device_bytes": int(info.device_bytes), "scratch_bytes_after_warmup": scratch_after_warmup,
                       "build_ms": round(float(info.build_ms), 1), "upload_ms": round(float(info.upload_ms), 1)},
             "timing": {"in_flight": Q, "submit_to_done_ms": round(statistics.mean(calls), 4),
                        "submit_us_per_frame": round(submit_s[0] * 1e6 / args.steps, 2),
-                       "one_frame_ms": round(sync_ms, 4), "kernel_ms": round(kernel_ms, 4),
+                       "one_frame_ms": None if sync_ms is None else round(sync_ms, 4),
+                       "kernel_ms": None if kernel_ms is None else round(kernel_ms, 4),
                        "what": "frames pipelined with in_flight renders submitted (rt_render_submit) before the "
                                "oldest is waited for (rt_render_wait); submit_to_done_ms = a pipelined frame's "
                                "latency from submit to image complete in host memory; one_frame_ms = the same for "
                                "one frame at a time (rt_render_ex, RenderStats.milliseconds); kernel_ms = HIP events "
-                               "around the render launch in those single frames"},
+                               "around the render launch in those single frames (both measured with --full only)"},
             "roofline": roofline,
             "cpu_baseline": cpu,
             "gather": gather,
@@ -573,6 +629,29 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_CAP_BYTES = 48 << 20      # --dump-outputs: everything written stays under 64 MB
+
+
+def dump_outputs(path, frame, stats):
+    """--dump-outputs: what the last timed step delivered, as DIR/<name>.npy.  `frame` is the
+    RGBA8 image in host memory (H, W, 4), written as float32 (exact for 8-bit values); a frame
+    whose float32 copy and pixel indices would pass DUMP_CAP_BYTES is written as a fixed, seeded
+    sample of its pixels (rgba8: (n, 4); rgba8_pixels: their row-major indices, float64).
+    ray_counts: the frame's counters on this rank, float64."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    H, W, C = frame.shape
+    if H * W * C * 4 <= DUMP_CAP_BYTES:
+        np.save(os.path.join(path, "rgba8.npy"), np.asarray(frame, dtype=np.float32))
+    else:
+        n = DUMP_CAP_BYTES // (C * 4 + 8)
+        px = np.sort(np.random.default_rng(20240229).choice(H * W, size=n, replace=False))
+        np.save(os.path.join(path, "rgba8.npy"), np.asarray(frame.reshape(H * W, C)[px], dtype=np.float32))
+        np.save(os.path.join(path, "rgba8_pixels.npy"), px.astype(np.float64))
+    counts = [stats.primary_rays, stats.shadow_rays, stats.shadow_rays_traced, stats.secondary_rays]
+    np.save(os.path.join(path, "ray_counts.npy"), np.array(counts, dtype=np.float64))
 
 
 def roofline_fields(args, eng, dev, first, step, rows, W, kernel_ms, rays_rank, world):

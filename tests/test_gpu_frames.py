@@ -194,7 +194,7 @@ def test_bench_strong_split_two_ranks_gathers_the_same_frame():
     """`bench.py --gpus 2` (torchrun started by bench.py, both ranks pinned to this GPU): one C2
     frame per step, chunks split over the ranks, rows stored into one shared page-locked
     framebuffer - complete and bit-identical to the 1-GPU frame."""
-    common = ["--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-side-paths"]
+    common = ["--full", "--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-side-paths"]
     one = _bench(["--gpus", "1"] + common, {})
     two = _bench(["--gpus", "2"] + common, {"MYRT_BENCH_DEVICE": "0"})
     two_staged = _bench(["--gpus", "2", "--gather", "staged"] + common, {"MYRT_BENCH_DEVICE": "0"})
@@ -205,6 +205,37 @@ def test_bench_strong_split_two_ranks_gathers_the_same_frame():
     assert two["rays"]["per_step"] == one["rays"]["per_step"]
 
 
+def test_bench_plain_run_times_the_steps_and_dumps_the_last_frame(tmp_path, scene_dir):
+    """A plain `bench.py` run (no --full): the line carries the headline figure and
+    ms_per_step for exactly --steps timed steps, everything measured beside it is null, and
+    --dump-outputs writes the frame the last timed step delivered - C2's frame, equal to the
+    engine's own RGBA8 render - with its ray counts."""
+    out = tmp_path / "dump"
+    line = _bench(["--gpus", "1", "--config", "c2", "--steps", "5", "--warmup", "1", "--dump-outputs", str(out)], {})
+    assert line["full"] is False and line["steps"] == 5 and line["warmup"] == 1
+    assert line["unit"] == "Mrays/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0
+    # the line rounds ms_per_step to 1e-4 ms and value to 0.01
+    assert line["value"] == pytest.approx(line["rays"]["per_step"] / (line["ms_per_step"] * 1e-3) / 1e6,
+                                          rel=1e-4 + 1e-4 / line["ms_per_step"])
+    for k in ("roofline", "cpu_baseline", "gather", "side_paths", "per_rank", "numa"):
+        assert line[k] is None, k
+    assert line["timing"]["kernel_ms"] is None and line["timing"]["one_frame_ms"] is None
+    assert sorted(os.listdir(out)) == ["ray_counts.npy", "rgba8.npy"]
+    got = np.load(out / "rgba8.npy")
+    assert got.dtype == np.float32 and got.shape == (600, 800, 4)
+    eng = M.RayTracerEngine(scenes.scene_c2(path_dir=scene_dir))
+    rgba = M.pinned_array((600, 800, 4), np.uint8)
+    rgba.fill(0)
+    st = eng.render_into(0, 0, 1, rgb=None, rgba=rgba, frame_layout=True)
+    eng.close()
+    assert np.array_equal(got, rgba)
+    rc = np.load(out / "ray_counts.npy")
+    assert rc.dtype == np.float64
+    assert rc.tolist() == [st.primary_rays, st.shadow_rays, st.shadow_rays_traced, st.secondary_rays]
+    assert line["rays"]["per_step"] == st.primary_rays + st.shadow_rays_traced
+
+
 @pytest.mark.timeout(600)
 def test_bench_strong_split_eight_ranks_on_one_gpu():
     """The C4 process path at N = 8 (Object+Extension.swift:75-82): `bench.py --gpus 8` with
@@ -212,7 +243,7 @@ def test_bench_strong_split_eight_ranks_on_one_gpu():
     C2, 3 steps: 8 processes, 16 shared registered framebuffers, chunk c on rank c mod 8.  The
     gathered frame is complete and bit-identical to the 1-GPU frame, and the line carries
     every rank's timing."""
-    common = ["--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-side-paths"]
+    common = ["--full", "--config", "c2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-side-paths"]
     one = _bench(["--gpus", "1"] + common, {})
     eight = _bench(["--gpus", "8"] + common, {"MYRT_BENCH_DEVICE": "0"})
     assert eight["n_gpus"] == 8 and eight["scaling"] == "strong"

@@ -213,6 +213,44 @@ def test_isa_loops_census():
     assert rows["BB0_2"]["depth"] == 2 and rows["BB0_2"]["scratch_ld"] == 1 and rows["BB0_2"]["valu"] == 1
 
 
+def test_dump_outputs_whole_frame_and_seeded_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: a frame under the cap is written whole as float32; a larger one
+    as the same seeded pixel sample every time, with its indices, under the cap."""
+    import types
+    import numpy as np
+    frame = np.random.default_rng(3).integers(0, 256, (37, 53, 4), dtype=np.uint8)
+    st = types.SimpleNamespace(primary_rays=1961, shadow_rays=1200, shadow_rays_traced=900, secondary_rays=7)
+    bench.dump_outputs(str(tmp_path / "a"), frame, st)
+    got = np.load(tmp_path / "a" / "rgba8.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frame)
+    assert not (tmp_path / "a" / "rgba8_pixels.npy").exists()
+    rc = np.load(tmp_path / "a" / "ray_counts.npy")
+    assert rc.dtype == np.float64 and rc.tolist() == [1961, 1200, 900, 7]
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 24 * 500)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), frame, st)
+    px = np.load(tmp_path / "b" / "rgba8_pixels.npy")
+    got = np.load(tmp_path / "b" / "rgba8.npy")
+    assert px.dtype == np.float64 and got.dtype == np.float32 and got.shape == (500, 4)
+    idx = px.astype(np.int64)
+    assert len(set(idx.tolist())) == 500 and idx.min() >= 0 and idx.max() < 37 * 53
+    assert np.array_equal(got, frame.reshape(-1, 4)[idx])
+    assert got.nbytes + px.nbytes <= bench.DUMP_CAP_BYTES
+    assert np.array_equal(px, np.load(tmp_path / "c" / "rgba8_pixels.npy"))
+
+
+def test_scene_cache_dir_skips_what_cannot_be_written(tmp_path):
+    """bench.py's scene folder: the first candidate that can be created and written (a source
+    tree that is read-only for the user falls through to the next one)."""
+    blocker = tmp_path / "file"
+    blocker.write_text("x")
+    good = tmp_path / "cache" / "scenes"
+    assert bench.scene_cache_dir([str(blocker / "scenes_cache"), str(good), str(tmp_path / "later")]) == str(good)
+    assert good.is_dir() and not (tmp_path / "later").exists()
+    with pytest.raises(SystemExit):
+        bench.scene_cache_dir([str(blocker / "a"), str(blocker / "b")])
+
+
 def test_numa_helpers():
     """bench.py's NUMA fields: cpulist parsing / printing, the node map from
     sysfs, and the per-page node census of a buffer (move_pages with no target nodes)."""

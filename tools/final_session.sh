@@ -11,6 +11,8 @@ set -u
 T="${1:-r04z}"
 PART="${2:-all}"
 G="python3 bench.py --steps 10 --warmup 2 --in-flight 1 --no-cpu-baseline --no-side-paths"
+F="python3 bench.py --full"      # the bench lines kept as records carry every field
+O="$(sed -n 's/^mkdir -p //p' tools/gpu_session.sh)"      # the folder gpu_session.sh keeps its logs in
 VALU="GRBM_GUI_ACTIVE SQ_ACTIVE_INST_VALU SQ_THREAD_CYCLES_VALU SQ_INSTS_VALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY"
 if [ "$PART" = 1 ] || [ "$PART" = all ]; then
 bash tools/prof_session.sh ${T}_c3 || exit $?
@@ -26,14 +28,14 @@ fi
 [ "$PART" = 3 ] && exit 0
 bash tools/gpu_session.sh \
  "${T}_smoke|300|python3 -c 'import __graft_entry__ as g; g.smoke()'" \
- "${T}_bc3|300|python3 bench.py > gpurun_out/${T}_bench_c3.json" \
- "${T}_bc5|300|python3 bench.py --config c5 --steps 400 --warmup 20 --no-cpu-baseline > gpurun_out/${T}_bench_c5.json" \
- "${T}_bc3i|300|python3 bench.py --config c3i --steps 400 --warmup 20 --no-cpu-baseline > gpurun_out/${T}_bench_c3i.json" \
- "${T}_bc3g|300|python3 bench.py --config c3g --steps 60 --warmup 5 --no-cpu-baseline > gpurun_out/${T}_bench_c3g.json" \
- "${T}_bc3r|300|python3 bench.py --config c3r --steps 60 --warmup 5 --no-cpu-baseline > gpurun_out/${T}_bench_c3r.json" \
- "${T}_bc3d|300|python3 bench.py --config c3d --steps 60 --warmup 5 --no-cpu-baseline > gpurun_out/${T}_bench_c3d.json" \
- "${T}_bc2|300|python3 bench.py --config c2 --steps 2000 --warmup 50 > gpurun_out/${T}_bench_c2.json" \
- "${T}_bc3k|300|python3 bench.py --steps 2000 --warmup 50 --no-cpu-baseline > gpurun_out/${T}_bench_c3_2000.json" \
+ "${T}_bc3|300|$F > $O/${T}_bench_c3.json" \
+ "${T}_bc5|300|$F --config c5 --steps 400 --warmup 20 --no-cpu-baseline > $O/${T}_bench_c5.json" \
+ "${T}_bc3i|300|$F --config c3i --steps 400 --warmup 20 --no-cpu-baseline > $O/${T}_bench_c3i.json" \
+ "${T}_bc3g|300|$F --config c3g --steps 60 --warmup 5 --no-cpu-baseline > $O/${T}_bench_c3g.json" \
+ "${T}_bc3r|300|$F --config c3r --steps 60 --warmup 5 --no-cpu-baseline > $O/${T}_bench_c3r.json" \
+ "${T}_bc3d|300|$F --config c3d --steps 60 --warmup 5 --no-cpu-baseline > $O/${T}_bench_c3d.json" \
+ "${T}_bc2|300|$F --config c2 --steps 2000 --warmup 50 > $O/${T}_bench_c2.json" \
+ "${T}_bc3k|300|$F --steps 2000 --warmup 50 --no-cpu-baseline > $O/${T}_bench_c3_2000.json" \
  "${T}_c3g_trace|300|rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${T}_c3g_trace -- $G --config c3g" \
  "${T}_c3r_trace|300|rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/${T}_c3r_trace -- $G --config c3r" \
  "${T}_c3g_valu|300|timeout -s KILL 240 rocprofv3 --pmc $VALU --output-format csv -d gpurun_out/${T}_c3g_valu -- $G --config c3g" \
