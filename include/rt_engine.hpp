@@ -99,12 +99,14 @@ using ProgressFn = std::function<bool(const RenderProgress&)>;
 class RayTracerEngine {
 public:
     /* Builds the scene on the host (PLY, flattening, SAH BVH) and uploads a replica to
-     * every listed device (empty = device 0).  The descriptor is copied. */
+     * every listed device (empty = device 0).  The descriptor is copied.  dynamic: instances and
+     * cameras may move between renders (setTransform / setCamera / commit; RT_SCENE_DYNAMIC). */
     explicit RayTracerEngine(const rt_scene_desc& desc, std::vector<int32_t> devices = {},
-                             std::vector<CameraMeta> cameraMeta = {})
+                             std::vector<CameraMeta> cameraMeta = {}, bool dynamic = false)
         : meta_(std::move(cameraMeta)) {
         for (int32_t i = 0; i < desc.num_cameras; ++i) cams_.push_back(desc.cameras[i]);
-        check(rt_scene_create(&desc, devices.empty() ? nullptr : devices.data(), (int32_t)devices.size(), &scene_));
+        check(rt_scene_create_ex(&desc, devices.empty() ? nullptr : devices.data(), (int32_t)devices.size(),
+                                 dynamic ? RT_SCENE_DYNAMIC : 0u, &scene_));
     }
     /* RayTracerEngine.init(from: url) / init(data:) (RayTracer.swift:30-49): the scene file is
      * decoded by rt_scene_file_* (JSON or XML, ParsingKit's conventions), then built like the
@@ -143,6 +145,37 @@ public:
         int64_t v = 0;
         check(rt_scene_get_option(scene_, name.c_str(), &v));
         return v;
+    }
+
+    /* Dynamic scenes: RTContext.refitTLAS() (RTContext.swift:883-927).  instanceOf: the instance
+     * scene object `objectIndex` produced (-1: none).  setTransform stages a column-major
+     * localToWorld for that instance until commit(); setCamera replaces a camera at once; commit()
+     * refits every acceleration structure on every replica and blocks until they are updated.
+     * commit and setCamera throw RenderError(RT_ERR_BUSY) while a submitted render has not been
+     * waited for; setTransform and commit throw RT_ERR_UNSUPPORTED on an engine built without
+     * `dynamic`. */
+    int32_t instanceOf(int32_t objectIndex) const {
+        int32_t k = -1;
+        check(rt_scene_instance_of_object(scene_, objectIndex, &k));
+        return k;
+    }
+    void setTransform(int32_t objectIndex, const double m[16]) {
+        const int32_t k = instanceOf(objectIndex);
+        if (k < 0) throw RenderError(RT_ERR_INVALID_ARG, "the object produced no instance");
+        check(rt_scene_set_instance_transform(scene_, k, m));
+    }
+    void setCamera(int32_t index, const rt_camera& camera) {
+        check(rt_scene_set_camera(scene_, index, &camera));
+        cams_.at((size_t)index) = camera;
+    }
+    rt_commit_stats commit() {
+        rt_commit_stats st{};
+        check(rt_scene_commit(scene_, &st));
+        return st;
+    }
+    /* Instance.worldBounds of an instance (any scene), as of the last commit. */
+    void instanceBounds(int32_t instance, double lo[3], double hi[3]) const {
+        check(rt_scene_instance_bounds(scene_, instance, lo, hi));
     }
 
 private:

@@ -49,8 +49,11 @@
  *      structs grew); rt_scene_set_option / rt_scene_get_option replace the MYRT_*
  *      environment switches (the library reads no environment variable on the render path).
  *   4: the test hooks debug_fail_replica / wide_delta_scale moved behind the non-production
- *      rt_scene_set_unsafe_option; rt_scene_set_option refuses them. */
-#define RT_ABI_VERSION 4
+ *      rt_scene_set_unsafe_option; rt_scene_set_option refuses them.
+ *   5: dynamic scenes (appended, nothing existing changed): rt_scene_create_ex with
+ *      RT_SCENE_DYNAMIC, rt_scene_instance_of_object, rt_scene_set_instance_transform,
+ *      rt_scene_set_camera, rt_scene_instance_bounds, rt_scene_commit. */
+#define RT_ABI_VERSION 5
 
 #ifdef __cplusplus
 extern "C" {
@@ -196,6 +199,52 @@ int32_t rt_scene_create(const rt_scene_desc* desc, const int32_t* devices, int32
                         rt_scene** out);
 void    rt_scene_destroy(rt_scene* scene);
 int32_t rt_scene_info_get(const rt_scene* scene, rt_scene_info* out);
+
+/* ---- dynamic scenes (ABI 5) ------------------------------------------------------
+ * RTContext.refitTLAS() (RayTracer/Models/RTContext.swift:883-927, "for animation frames") and
+ * BVHBuilder.refit (RayTracer/Accelearion/BVH.swift:254-291).  A scene created with
+ * RT_SCENE_DYNAMIC accepts new localToWorld matrices for its instances between renders;
+ * rt_scene_commit then brings every acceleration structure up to date with the reference's refit
+ * semantics: the TLAS keeps its topology and its bounds are recomputed bottom-up from the
+ * instances' new world bounds.  No PLY is parsed again and no BLAS rebuilt.  Instances can not
+ * be added or removed, and vertices do not move.  A dynamic scene always uses the transformed
+ * layout (also while every matrix is the identity); scenes created without the flag behave
+ * exactly as before.
+ *   rt_scene_create_ex               rt_scene_create with flags (rt_scene_create == flags 0).
+ *   rt_scene_instance_of_object      the instance scene object `object_index` produced
+ *                                    (*instance = -1: none, e.g. an empty mesh).
+ *   rt_scene_set_instance_transform  stages a matrix (column-major) until the next commit; renders
+ *                                    before the commit see the old pose.  RT_ERR_UNSUPPORTED on a
+ *                                    scene without RT_SCENE_DYNAMIC; RT_ERR_INVALID_ARG (and nothing
+ *                                    staged) for a non-finite entry or an upper 3x3 determinant that
+ *                                    is 0 or non-finite.
+ *   rt_scene_set_camera              replaces camera `camera_index` of any scene, at once.
+ *   rt_scene_instance_bounds         Instance.worldBounds of any scene's instance (as of the last
+ *                                    commit).
+ *   rt_scene_commit                  applies the staged transforms on every device replica and
+ *                                    blocks until all are updated.  With nothing staged it is legal
+ *                                    and changes nothing.  RT_ERR_UNSUPPORTED without
+ *                                    RT_SCENE_DYNAMIC; RT_ERR_INVALID_ARG (nothing changed, the
+ *                                    staged transforms dropped) when a transform puts an instance
+ *                                    beyond 1e30.
+ * rt_scene_commit and rt_scene_set_camera return RT_ERR_BUSY, and change nothing, while a render
+ * submitted with rt_render_submit has not been waited for.  Renders enqueued with rt_render_device
+ * on caller streams are the caller's to order: synchronise those streams before a commit or a
+ * camera change.  Both calls drop the measured tile orders (option tile_order) they make stale. */
+#define RT_SCENE_DYNAMIC 1u
+int32_t rt_scene_create_ex(const rt_scene_desc* desc, const int32_t* devices, int32_t n_devices,
+                           uint32_t flags, rt_scene** out);
+int32_t rt_scene_instance_of_object(const rt_scene* scene, int32_t object_index, int32_t* instance);
+int32_t rt_scene_set_instance_transform(rt_scene* scene, int32_t instance, const double m[16]);
+int32_t rt_scene_set_camera(rt_scene* scene, int32_t camera_index, const rt_camera* camera);
+int32_t rt_scene_instance_bounds(const rt_scene* scene, int32_t instance, double lo[3], double hi[3]);
+typedef struct rt_commit_stats {
+    int64_t instances_moved;
+    double  bounds_ms;          /* instance world bounds (device reduction + host)     */
+    double  refit_ms;           /* host TLAS refit + uploads + device tree refit        */
+    double  total_ms;
+} rt_commit_stats;
+int32_t rt_scene_commit(rt_scene* scene, rt_commit_stats* stats /* may be NULL */);
 
 /* Render options: tuning and test switches, each default being the production setting.
  *   wide (1)             conservative FP32 four-wide walk of identity scenes (exact: wide.h)

@@ -62,6 +62,7 @@ class rt_scene_desc(C.Structure):
 
 RT_RENDER_FRAME_LAYOUT = 1
 RT_RENDER_KERNEL_TIME = 2
+RT_SCENE_DYNAMIC = 1
 RT_SCENE_FORMAT_AUTO, RT_SCENE_FORMAT_JSON, RT_SCENE_FORMAT_XML = 0, 1, 2
 
 
@@ -77,6 +78,11 @@ class rt_scene_info(C.Structure):
                 ("instances", C.c_int64), ("blas_nodes", C.c_int64), ("tlas_nodes", C.c_int64),
                 ("max_depth", C.c_int64), ("build_ms", C.c_double), ("upload_ms", C.c_double),
                 ("device_bytes", C.c_int64), ("scratch_bytes", C.c_int64)]
+
+
+class rt_commit_stats(C.Structure):
+    _fields_ = [("instances_moved", C.c_int64), ("bounds_ms", C.c_double), ("refit_ms", C.c_double),
+                ("total_ms", C.c_double)]
 
 
 class rt_work_counters(C.Structure):
@@ -132,8 +138,10 @@ EXPORTED_SYMBOLS = [
     "rt_scene_file_load", "rt_scene_file_parse", "rt_scene_file_desc", "rt_scene_file_image_name",
     "rt_scene_file_last_error", "rt_scene_file_destroy", "rt_scene_set_option", "rt_scene_get_option",
     "rt_scene_set_unsafe_option",
+    "rt_scene_create_ex", "rt_scene_instance_of_object", "rt_scene_set_instance_transform", "rt_scene_set_camera",
+    "rt_scene_instance_bounds", "rt_scene_commit",
 ]
-RT_ABI_VERSION = 4
+RT_ABI_VERSION = 5
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
@@ -220,4 +228,17 @@ def bind(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "rt_scene_set_unsafe_option"):   # ABI >= 4 (test hooks, not for production)
         lib.rt_scene_set_unsafe_option.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
         lib.rt_scene_set_unsafe_option.restype = C.c_int32
+    if hasattr(lib, "rt_scene_commit"):   # ABI >= 5 (dynamic scenes)
+        lib.rt_scene_create_ex.argtypes = [P(rt_scene_desc), c_int32_p, C.c_int32, C.c_uint32, P(C.c_void_p)]
+        lib.rt_scene_create_ex.restype = C.c_int32
+        lib.rt_scene_instance_of_object.argtypes = [C.c_void_p, C.c_int32, c_int32_p]
+        lib.rt_scene_instance_of_object.restype = C.c_int32
+        lib.rt_scene_set_instance_transform.argtypes = [C.c_void_p, C.c_int32, c_double_p]
+        lib.rt_scene_set_instance_transform.restype = C.c_int32
+        lib.rt_scene_set_camera.argtypes = [C.c_void_p, C.c_int32, P(rt_camera)]
+        lib.rt_scene_set_camera.restype = C.c_int32
+        lib.rt_scene_instance_bounds.argtypes = [C.c_void_p, C.c_int32, c_double_p, c_double_p]
+        lib.rt_scene_instance_bounds.restype = C.c_int32
+        lib.rt_scene_commit.argtypes = [C.c_void_p, P(rt_commit_stats)]
+        lib.rt_scene_commit.restype = C.c_int32
     return lib

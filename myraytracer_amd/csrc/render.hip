@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -29,6 +30,7 @@
 #include "../../include/rtcore.h"
 #include "device.h"
 #include "layout.h"
+#include "refit.h"
 #include "scene.h"
 
 namespace myrt {
@@ -1342,6 +1344,14 @@ struct DeviceReplica {
     Flight fl[kInFlight];                     // rt_render_submit slots
     std::vector<TileOrder> orders;            // tile orders by camera and chunk selection (option tile_order)
     int64_t order_clock = 0;
+    // dynamic scenes (rt_scene_commit, refit.h): the triangles' exact local boxes when the scene has
+    // no CTri, the per-level node lists of the TLAS's four-wide nodes and of the flattened instance
+    // tree, and (replica 0) the scratch of the instance-bounds reduction
+    double* pbox = nullptr;
+    int32_t* tlas_levels = nullptr;
+    int32_t* fit_levels = nullptr;
+    dev::RefitMove* moves = nullptr; double* bounds_part = nullptr; double* bounds_out = nullptr;
+    int64_t moves_cap = 0, bounds_part_cap = 0;
 };
 
 }  // namespace
@@ -1406,6 +1416,8 @@ struct rt_scene {
         bool waiting = false;                     // a thread is blocked in rt_render_wait on it
     } flights[RT_MAX_IN_FLIGHT];
     int64_t next_ticket = 0;
+    // dynamic scenes: transforms staged by rt_scene_set_instance_transform until rt_scene_commit
+    std::vector<std::pair<int32_t, std::array<double, 16>>> staged;
 };
 
 static int64_t full_scratch_bytes(const FullScratch& f) {
@@ -1492,6 +1504,8 @@ static void free_replica(DeviceReplica& r) {
     (void)hipFree(r.tlas_leaf); (void)hipFree(r.mats); (void)hipFree(r.plights); (void)hipFree(r.counters);
     (void)hipFree(r.alights); (void)hipFree(r.jitter); (void)hipFree(r.wave_times);
     (void)hipFree(r.deep);
+    (void)hipFree(r.pbox); (void)hipFree(r.tlas_levels); (void)hipFree(r.fit_levels);
+    (void)hipFree(r.moves); (void)hipFree(r.bounds_part); (void)hipFree(r.bounds_out);
     r.full.release();
     r.dev_full.release();
     (void)hipFree(r.arena.base);
@@ -1583,6 +1597,11 @@ static int32_t make_replica(const HostScene& S, int device, DeviceReplica& r, co
     if ((rc = upload(S.plights, &r.plights, r.bytes)) != RT_OK) return rc;
     if ((rc = upload(S.alights, &r.alights, r.bytes)) != RT_OK) return rc;
     if ((rc = upload(S.jitter, &r.jitter, r.bytes)) != RT_OK) return rc;
+    if (S.dynamic) {
+        if (!S.dyn.pbox.empty() && (rc = upload(S.dyn.pbox, &r.pbox, r.bytes)) != RT_OK) return rc;
+        if ((rc = upload(S.dyn.tlas_levels.nodes, &r.tlas_levels, r.bytes)) != RT_OK) return rc;
+        if ((rc = upload(S.dyn.fit_levels.nodes, &r.fit_levels, r.bytes)) != RT_OK) return rc;
+    }
     HIP_TRY(hipMalloc((void**)&r.counters, kCounterWords * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(r.counters, 0, kCounterWords * sizeof(unsigned long long)));
     HIP_TRY(hipMalloc((void**)&r.dev_counters, kCounterWords * sizeof(unsigned long long)));
@@ -1733,7 +1752,7 @@ static double dist_to_center(const HostScene& S, const double p[3]) {
 // FP32 rounding of the slab terms (wide.h header); weps = eps rounded down to float.
 // Transformed scenes with a flattened instance tree (option fit): R also covers the tree's
 // magnitudes (fit_coord) and wdelta carries 2^-27 R more for the world <-> local rounding (wide.h
-// fit_walk header); the larger widening only loosens tw_walk's TLAS filter.
+// fit_walk header); with the option off neither applies (the render is tw_walk alone).
 static void set_wide(const HostScene& S, const DeviceReplica& r, RenderParams& P, double origin_coord, bool on,
                      int64_t scale_permille, bool fit) {
     P.wnodes = r.wnodes; P.lbox = r.lbox; P.wide_root = S.wide_root;
@@ -1741,10 +1760,13 @@ static void set_wide(const HostScene& S, const DeviceReplica& r, RenderParams& P
     P.winst = S.winst.empty() ? nullptr : r.winst;          // transformed scenes (wide.h tw_walk)
     P.tw_tlas_nodes = (int32_t)S.tw_tlas_nodes;
     P.tw_wscale = (float)((double)scale_permille * 1e-3);
-    const bool has_fit = S.fit_root >= 0 && !S.fpairs.empty() && r.fpairs;
-    const double R = std::max({S.wide_coord, has_fit ? S.fit_coord : 0.0, origin_coord}) + std::fabs(S.shadow_eps) +
+    const bool has_fit = S.fit_root >= 0 && !S.fpairs.empty() && r.fpairs && !S.dyn.fit_blocked;
+    // the fit tree's magnitudes and its extra widening count only when the fit walk is on: with
+    // option fit = 0 the render is the plain tw_walk, and a large fit_coord does not cost it P.wide
+    const bool use_fit = has_fit && fit;
+    const double R = std::max({S.wide_coord, use_fit ? S.fit_coord : 0.0, origin_coord}) + std::fabs(S.shadow_eps) +
                      std::fabs(S.eps);
-    P.wdelta = R * (has_fit ? 0x1p-21 + 0x1p-27 : 0x1p-21) * ((double)scale_permille * 1e-3);
+    P.wdelta = R * (use_fit ? 0x1p-21 + 0x1p-27 : 0x1p-21) * ((double)scale_permille * 1e-3);
     float we = (float)S.eps;
     if ((double)we > S.eps) we = std::nextafter(we, -HUGE_VALF);
     P.weps = we;
@@ -2329,11 +2351,18 @@ const char* rt_last_error(void) { return g_err.c_str(); }
 const char* rt_version(void) { return "myraytracer_amd 0.2 (abi " MYRT_STR(RT_ABI_VERSION) ", gfx950, fp64)"; }
 
 int32_t rt_scene_create(const rt_scene_desc* desc, const int32_t* devices, int32_t n_devices, rt_scene** out) {
+    return rt_scene_create_ex(desc, devices, n_devices, 0u, out);
+}
+
+int32_t rt_scene_create_ex(const rt_scene_desc* desc, const int32_t* devices, int32_t n_devices, uint32_t flags,
+                           rt_scene** out) {
     if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!desc) return fail(RT_ERR_NO_SCENE, "No scene loaded. Can't render.");
+    if (flags & ~RT_SCENE_DYNAMIC) return fail(RT_ERR_INVALID_ARG, "unknown scene flags");
     try {
         auto* s = new rt_scene();
+        s->host.dynamic = (flags & RT_SCENE_DYNAMIC) != 0;
         std::string err;
         int32_t rc = build_host_scene(desc, s->host, err);
         if (rc != RT_OK) { delete s; return fail(rc, err); }
@@ -2373,6 +2402,7 @@ int32_t rt_scene_create(const rt_scene_desc* desc, const int32_t* devices, int32
         s->host.normals.clear(); s->host.normals.shrink_to_fit();
         s->host.wnodes.clear(); s->host.wnodes.shrink_to_fit();
         s->host.lbox.clear(); s->host.lbox.shrink_to_fit();
+        s->host.dyn.pbox.clear(); s->host.dyn.pbox.shrink_to_fit();
         *out = s;
         return RT_OK;
     } catch (const std::bad_alloc&) {
@@ -2431,6 +2461,228 @@ int32_t rt_scene_get_option(const rt_scene* s, const char* name, int64_t* value)
     for (int k = 0; k < kOptCount; ++k)
         if (std::strcmp(name, kOptDefs[k].name) == 0) { *value = s->opt[k]; return RT_OK; }
     return fail(RT_ERR_INVALID_ARG, std::string("unknown option ") + name);
+}
+
+// ---- dynamic scenes: instances and cameras move between renders (rtcore.h, ABI 5) -----------------
+static bool scene_busy(const rt_scene* s) {
+    for (const rt_scene::Pending& fp : s->flights)
+        if (fp.pending) return true;
+    return false;
+}
+// The measured tile orders belong to a camera and a pose: both setters drop them (the buffers are
+// retired, a device render still queued on a caller's stream may be writing its tile costs).
+static void drop_tile_orders(rt_scene* s) {
+    for (DeviceReplica& r : s->devs) {
+        for (TileOrder& o : r.orders) {
+            retire(r, o.order, o.n * 4); retire(r, o.cost, o.n * 16);
+            if (o.ev) (void)hipEventDestroy(o.ev);
+        }
+        r.orders.clear();
+    }
+}
+
+int32_t rt_scene_instance_of_object(const rt_scene* s, int32_t object_index, int32_t* instance) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!instance) return fail(RT_ERR_INVALID_ARG, "instance is NULL");
+    if (object_index < 0 || object_index >= (int32_t)s->host.object_inst.size())
+        return fail(RT_ERR_INVALID_ARG, "bad object index");
+    *instance = s->host.object_inst[(size_t)object_index];
+    return RT_OK;
+}
+
+int32_t rt_scene_set_instance_transform(rt_scene* s, int32_t instance, const double m[16]) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
+    if (instance < 0 || instance >= (int32_t)s->host.insts.size()) return fail(RT_ERR_INVALID_ARG, "bad instance index");
+    if (!m || !matrix_ok(m))
+        return fail(RT_ERR_INVALID_ARG, "localToWorld must be finite with a non-zero, finite upper 3x3 determinant");
+    std::array<double, 16> a;
+    std::memcpy(a.data(), m, sizeof(double) * 16);
+    std::lock_guard<std::mutex> lock(s->mu);
+    for (auto& e : s->staged)
+        if (e.first == instance) { e.second = a; return RT_OK; }
+    s->staged.push_back({instance, a});
+    return RT_OK;
+}
+
+int32_t rt_scene_set_camera(rt_scene* s, int32_t camera_index, const rt_camera* cam) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!cam) return fail(RT_ERR_INVALID_ARG, "camera is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (camera_index < 0 || camera_index >= (int32_t)s->host.cams.size())
+        return fail(RT_ERR_INVALID_CAMERA, "Invalid camera index");
+    if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
+    s->host.cams[(size_t)camera_index] = *cam;
+    drop_tile_orders(s);
+    return RT_OK;
+}
+
+int32_t rt_scene_instance_bounds(const rt_scene* s, int32_t instance, double lo[3], double hi[3]) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!lo || !hi) return fail(RT_ERR_INVALID_ARG, "NULL argument");
+    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
+    if (instance < 0 || 6 * (size_t)instance + 6 > s->host.inst_bounds.size())
+        return fail(RT_ERR_INVALID_ARG, "bad instance index");
+    const double* b = &s->host.inst_bounds[6 * (size_t)instance];
+    for (int k = 0; k < 3; ++k) { lo[k] = b[k]; hi[k] = b[3 + k]; }
+    return RT_OK;
+}
+
+// World bounds of the moved triangle-mesh instances, on replica 0 (refit.h k_inst_bounds)
+static int32_t device_instance_bounds(rt_scene* s, const std::vector<dev::RefitMove>& moves, std::vector<double>& out) {
+    DeviceReplica& r = s->devs[0];
+    const HostScene& S = s->host;
+    const int64_t n = (int64_t)moves.size();
+    out.assign(6 * (size_t)n, 0.0);
+    if (n == 0) return RT_OK;
+    HIP_TRY(hipSetDevice(r.device));
+    int64_t most = 1;
+    for (const dev::RefitMove& m : moves) most = std::max<int64_t>(most, m.tri_end - m.tri_first);
+    const int parts = (int)std::min<int64_t>(64, (most + dev::kBoundsBlock * 8 - 1) / (dev::kBoundsBlock * 8));
+    if (r.moves_cap < n) {
+        (void)hipFree(r.moves); (void)hipFree(r.bounds_out);
+        r.moves = nullptr; r.bounds_out = nullptr; r.moves_cap = 0;
+        HIP_TRY(hipMalloc((void**)&r.moves, (size_t)n * sizeof(dev::RefitMove)));
+        HIP_TRY(hipMalloc((void**)&r.bounds_out, (size_t)n * 6 * sizeof(double)));
+        r.moves_cap = n;
+    }
+    if (r.bounds_part_cap < n * parts) {
+        (void)hipFree(r.bounds_part);
+        r.bounds_part = nullptr; r.bounds_part_cap = 0;
+        HIP_TRY(hipMalloc((void**)&r.bounds_part, (size_t)(n * parts) * 6 * sizeof(double)));
+        r.bounds_part_cap = n * parts;
+    }
+    HIP_TRY(hipMemcpy(r.moves, moves.data(), (size_t)n * sizeof(dev::RefitMove), hipMemcpyHostToDevice));
+    const CTri* ct = S.compact_tris ? r.ctris : nullptr;
+    if (!ct && !r.pbox) return fail(RT_ERR_DEVICE, "dynamic scene without triangle boxes");
+    constexpr int64_t kBatch = 32768;                       // gridDim.y
+    for (int64_t b = 0; b < n; b += kBatch) {
+        const int64_t nb = std::min(kBatch, n - b);
+        hipLaunchKernelGGL(dev::k_inst_bounds, dim3((unsigned)parts, (unsigned)nb), dim3(dev::kBoundsBlock), 0, r.stream, ct,
+                           r.pbox, r.moves + b, r.bounds_part + (size_t)b * parts * 6);
+    }
+    hipLaunchKernelGGL(dev::k_inst_bounds_final, dim3((unsigned)n), dim3(64), 0, r.stream, r.bounds_part, parts,
+                       r.bounds_out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(r.stream));
+    HIP_TRY(hipMemcpy(out.data(), r.bounds_out, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// One four-wide tree of a replica brought up to date: a launch per level, deepest first, then the
+// eight octant copies of its nodes (refit.h)
+static void refit_tree(const HostScene& S, DeviceReplica& r, const RefitLevels& L, const int32_t* list, int32_t marker_base) {
+    if (L.nodes.empty() || !list) return;
+    dev::RefitTree T{};
+    T.nodes = r.wnodes; T.marker_base = marker_base; T.winst = r.winst; T.fpairs = r.fpairs; T.lbox = r.lbox;
+    T.insts = r.insts;
+    for (size_t l = 0; l + 1 < L.off.size(); ++l) {
+        T.list = list + L.off[l];
+        T.count = (int32_t)(L.off[l + 1] - L.off[l]);
+        if (T.count <= 0) continue;
+        hipLaunchKernelGGL(dev::k_refit_level, dim3((unsigned)((4 * (int64_t)T.count + 255) / 256)), dim3(256), 0, r.stream, T);
+    }
+    const int64_t n = (int64_t)L.nodes.size();
+    hipLaunchKernelGGL(dev::k_octant_copies, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.stream, r.wnodes, list, n,
+                       S.wide_copy);
+}
+
+int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
+    if (stats) *stats = rt_commit_stats{};
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
+    const auto t0 = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    if (s->staged.empty()) {
+        if (stats) stats->total_ms = ms_since(t0);
+        return RT_OK;
+    }
+    try {
+        HostScene& S = s->host;
+        const DynScene& Y = S.dyn;
+        std::vector<std::pair<int32_t, std::array<double, 16>>> staged;
+        staged.swap(s->staged);                              // a failed commit stages nothing
+        const size_t n = staged.size();
+        // 1. Instance.worldBounds of the moved instances: triangle meshes on the device (the union
+        //    over every triangle), spheres and planes (one primitive) here
+        std::vector<double> nb(6 * n, 0.0), devb;
+        std::vector<dev::RefitMove> moves;
+        std::vector<size_t> move_of;
+        for (size_t q = 0; q < n; ++q) {
+            const int32_t k = staged[q].first;
+            const DynBlas& y = Y.blas[(size_t)Y.inst_blas[(size_t)k]];
+            if (y.kind != kPrimTriangles) {
+                special_instance_bounds(S, k, staged[q].second.data(), &nb[6 * q], &nb[6 * q + 3]);
+                continue;
+            }
+            dev::RefitMove mv{};
+            std::memcpy(mv.m, staged[q].second.data(), sizeof(mv.m));
+            for (int a = 0; a < 3; ++a) mv.motion[a] = y.motion[a];
+            mv.tri_first = (int32_t)y.tri_first; mv.tri_end = (int32_t)y.tri_end;
+            mv.blur = !(y.motion[0] == 0 && y.motion[1] == 0 && y.motion[2] == 0) ? 1 : 0;
+            moves.push_back(mv);
+            move_of.push_back(q);
+        }
+        int32_t rc = device_instance_bounds(s, moves, devb);
+        if (rc != RT_OK) return rc;
+        for (size_t j = 0; j < move_of.size(); ++j) std::memcpy(&nb[6 * move_of[j]], &devb[6 * j], 6 * sizeof(double));
+        const double bounds_ms = ms_since(t0);
+        // 2. nothing is changed unless every moved instance stays in range (float boxes stay finite)
+        for (size_t q = 0; q < n; ++q) {
+            bool ok = true;
+            for (int a = 0; a < 6; ++a) ok = ok && std::isfinite(nb[6 * q + a]) && std::fabs(nb[6 * q + a]) < 1e30;
+            if (!S.winst.empty()) {
+                const double* m = staged[q].second.data();
+                double reach = 0.0;
+                for (int a = 0; a < 16; ++a) reach = std::max(reach, std::fabs(m[a]));
+                ok = ok && reach * (3.0 * S.winst[(size_t)staged[q].first].bcoord + 1.0) < 1e30;
+            }
+            if (!ok) return fail(RT_ERR_INVALID_ARG, "a staged transform puts its instance out of range");
+        }
+        // 3. host: DInstance, TLAS bounds bottom-up, TLAS records, tbox, the margins' constants
+        const auto t1 = std::chrono::steady_clock::now();
+        for (size_t q = 0; q < n; ++q) {
+            set_instance_matrix(S, staged[q].first, staged[q].second.data());
+            std::memcpy(&S.inst_bounds[6 * (size_t)staged[q].first], &nb[6 * q], 6 * sizeof(double));
+        }
+        std::string err;
+        rc = refit_host_scene(S, err);
+        if (rc != RT_OK) return fail(rc, err);
+        // 4. every replica: instances, TLAS records, tbox; then the four-wide trees on its stream
+        for (DeviceReplica& r : s->devs) {
+            HIP_TRY(hipSetDevice(r.device));
+            HIP_TRY(hipMemcpy(r.insts, S.insts.data(), S.insts.size() * sizeof(DInstance), hipMemcpyHostToDevice));
+            if (!Y.tlas_recs.empty())
+                HIP_TRY(hipMemcpy(r.recs + S.blas_records, Y.tlas_recs.data(), Y.tlas_recs.size() * sizeof(WRec),
+                                  hipMemcpyHostToDevice));
+            if (!S.winst.empty() && r.wnodes) {
+                HIP_TRY(hipMemcpy(r.winst, S.winst.data(), S.winst.size() * sizeof(DWideInst), hipMemcpyHostToDevice));
+                refit_tree(S, r, Y.tlas_levels, r.tlas_levels, (int32_t)(S.tlas_leaf_base + (int64_t)S.tlas_leaf.size()));
+                if (S.fit_root >= 0) refit_tree(S, r, Y.fit_levels, r.fit_levels, -1);
+                HIP_TRY(hipGetLastError());
+            }
+        }
+        for (DeviceReplica& r : s->devs) {
+            HIP_TRY(hipSetDevice(r.device));
+            HIP_TRY(hipStreamSynchronize(r.stream));
+        }
+        drop_tile_orders(s);
+        if (stats) {
+            stats->instances_moved = (int64_t)n;
+            stats->bounds_ms = bounds_ms;
+            stats->refit_ms = ms_since(t1);
+            stats->total_ms = ms_since(t0);
+        }
+        return RT_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    } catch (const std::exception& e) {
+        return fail(RT_ERR_INVALID_ARG, e.what());
+    }
 }
 
 int32_t rt_render_device(rt_scene* s, int32_t slot, int32_t cam, int32_t first, int32_t step, double* d_rgb,

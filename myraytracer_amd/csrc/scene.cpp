@@ -386,7 +386,7 @@ struct BlasBuild {
     int64_t tri_first = 0, tri_end = 0;   // run of this BLAS's TriRecs in HostScene::tris
     double root_lo[3], root_hi[3];
 };
-struct InstBuild { int blas; double M[16]; int material; D3 motion; double wlo[3], whi[3]; };
+struct InstBuild { int blas; double M[16]; int material; D3 motion; double wlo[3], whi[3]; int obj; };
 }  // namespace
 
 // Lay one reference-form BVH out as WRec records.  Inner nodes get records in DFS
@@ -827,10 +827,12 @@ static void build_fit(HostScene& S) {
         };
         auto size_of = [&](int64_t r) { return B.isLeaf(r) ? B.count[r] : 2; };
         auto term = [&](int64_t r) { return r < 0 || (B.isLeaf(r) && B.count[r] == 1); };
-        std::function<void(int64_t, int64_t)> coll = [&](int64_t r, int64_t depth) {
+        // coll lays out the node whose children are `c`.  The builder leaves a leaf of any size when no
+        // split separates its pairs (five or more pairs with one centroid: instances stacked at one
+        // pose), so c may hold more than four pairs: they are then split into four consecutive
+        // groups, each a child node of its own, so that every pair stays in the tree.
+        std::function<void(std::vector<int64_t>, int64_t)> coll = [&](std::vector<int64_t> c, int64_t depth) {
             out.depth = std::max(out.depth, depth);
-            std::vector<int64_t> c;
-            expand(r, c);
             for (;;) {
                 int best = -1;
                 double bestA = -1.0;
@@ -847,32 +849,49 @@ static void build_fit(HostScene& S) {
             }
             const size_t idx = out.nodes.size();
             out.nodes.emplace_back();
+            // the node's slots: c itself, or (more than four pairs) four consecutive parts of it
+            const size_t nc = c.size(), ns = std::min<size_t>(nc, 4);
             int32_t refs[4] = {0, 0, 0, 0};
-            for (size_t i = 0; i < c.size(); ++i) {
-                if (term(c[i])) {
-                    const int64_t pi = c[i] < 0 ? ~c[i] : B.primIdx[B.leftFirst[c[i]]];
+            double blo[4][3], bhi[4][3];
+            for (size_t i = 0; i < ns; ++i) {
+                const size_t a = nc <= 4 ? i : nc * i / 4, b = nc <= 4 ? i + 1 : nc * (i + 1) / 4;
+                for (int y = 0; y < 3; ++y) { blo[i][y] = kInf; bhi[i][y] = -kInf; }
+                for (size_t m = a; m < b; ++m) {
+                    const double* lo = c[m] >= 0 ? &B.lo[3 * c[m]] : items[~c[m]].lo;
+                    const double* hi = c[m] >= 0 ? &B.hi[3 * c[m]] : items[~c[m]].hi;
+                    for (int y = 0; y < 3; ++y) { blo[i][y] = fmn(blo[i][y], lo[y]); bhi[i][y] = fmx(bhi[i][y], hi[y]); }
+                }
+                if (b - a > 1) {                              // a group of pairs: a child node
+                    refs[i] = (int32_t)out.nodes.size();
+                    coll(std::vector<int64_t>(c.begin() + a, c.begin() + b), depth + 1);
+                } else if (term(c[a])) {
+                    const int64_t pi = c[a] < 0 ? ~c[a] : B.primIdx[B.leftFirst[c[a]]];
                     refs[i] = ~(int32_t)out.pairs.size();
                     out.pairs.push_back({items[pi].t0, items[pi].inst});
                 } else {
                     refs[i] = (int32_t)out.nodes.size();
-                    coll(c[i], depth + 1);
+                    std::vector<int64_t> e;
+                    expand(c[a], e);
+                    coll(std::move(e), depth + 1);
                 }
             }
             W4Node& n = out.nodes[idx];
             std::memset(&n, 0, sizeof(n));
             for (int q = 0; q < 4; ++q) {
-                const bool has = q < (int)c.size();
-                const double* lo = !has ? nullptr : c[q] >= 0 ? &B.lo[3 * c[q]] : items[~c[q]].lo;
-                const double* hi = !has ? nullptr : c[q] >= 0 ? &B.hi[3 * c[q]] : items[~c[q]].hi;
+                const bool has = q < (int)ns;
                 for (int y = 0; y < 3; ++y) {
-                    n.pnear[y][q] = has ? WideBuilder::down(lo[y]) : HUGE_VALF;
-                    n.pfar[y][q] = has ? WideBuilder::up(hi[y]) : HUGE_VALF;
+                    n.pnear[y][q] = has ? WideBuilder::down(blo[q][y]) : HUGE_VALF;
+                    n.pfar[y][q] = has ? WideBuilder::up(bhi[q][y]) : HUGE_VALF;
                 }
                 n.ref[q] = refs[q];
             }
         };
         out.nodes.reserve(items.size() / 2 + 4);
-        coll(0, 1);
+        {
+            std::vector<int64_t> top;
+            expand(0, top);
+            coll(std::move(top), 1);
+        }
     }
     if (3 * out.depth + 2 > kStackCap) return;
     const int64_t node_base = (int64_t)S.wnodes.size();
@@ -1028,7 +1047,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
     std::vector<Tri> triangles;
     std::vector<BlasBuild> blases;
     std::vector<InstBuild> insts;
-    struct Base { int blas; int material; double M[16]; };
+    struct Base { int blas; int material; double M[16]; int obj; };
     std::map<int, Base> instanceByID;
     std::vector<int> meshOrder;
     std::vector<const rt_object*> meshInstances;
@@ -1052,6 +1071,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         return bb;
     };
 
+    std::vector<int> meshInstanceObj;
     for (int oi = 0; oi < d->num_objects; ++oi) {
         const rt_object& o = d->objects[oi];
         if (o.kind == RT_OBJ_SPHERE || o.kind == RT_OBJ_PLANE) {            // RTContext.swift:122-192
@@ -1084,6 +1104,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
             ib.blas = (int)blases.size() - 1;
             std::memcpy(ib.M, o.transform, sizeof(ib.M));
             ib.material = o.material_id; ib.motion = d3(0, 0, 0);
+            ib.obj = oi;
             insts.push_back(ib);
             continue;
         }
@@ -1094,10 +1115,11 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
             ib.blas = (int)blases.size() - 1;
             std::memcpy(ib.M, o.transform, sizeof(ib.M));
             ib.material = o.material_id; ib.motion = d3(0, 0, 0);
+            ib.obj = oi;
             insts.push_back(ib);
             continue;
         }
-        if (o.kind == RT_OBJ_MESH_INSTANCE) { meshInstances.push_back(&o); continue; }
+        if (o.kind == RT_OBJ_MESH_INSTANCE) { meshInstances.push_back(&o); meshInstanceObj.push_back(oi); continue; }
         if (o.kind != RT_OBJ_MESH) { err = "unknown object kind"; return RT_ERR_INVALID_ARG; }
         // ---- Mesh (RTContext.swift:242-377)
         S.n_meshes++;
@@ -1194,6 +1216,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
             blases.push_back(std::move(bb));
             Base base{};
             base.blas = (int)blases.size() - 1; base.material = o.material_id;
+            base.obj = oi;
             std::memcpy(base.M, o.transform, sizeof(base.M));
             instanceByID[o.id] = base;
         } else {
@@ -1201,15 +1224,18 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         }
     }
     // MeshInstance objects (RTContext.swift:384-401), then base meshes in scene order (:403-410, H11)
-    for (const rt_object* mi : meshInstances) {
+    for (size_t q = 0; q < meshInstances.size(); ++q) {
+        const rt_object* mi = meshInstances[q];
         auto it = instanceByID.find(mi->base_mesh_id);
         if (it == instanceByID.end()) continue;
         InstBuild ib{};
         ib.blas = it->second.blas;
         std::memcpy(ib.M, mi->transform, sizeof(ib.M));
         ib.material = mi->material_id; ib.motion = of(mi->motion_blur);
+        ib.obj = meshInstanceObj[q];
         insts.push_back(ib);
         Base nb{}; nb.blas = it->second.blas; nb.material = mi->material_id; std::memcpy(nb.M, mi->transform, sizeof(nb.M));
+        nb.obj = -1;                       // a mesh id taken over by an instance: no object of its own
         instanceByID[mi->id] = nb;
     }
     for (int meshID : meshOrder) {
@@ -1219,8 +1245,12 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         ib.blas = it->second.blas;
         std::memcpy(ib.M, it->second.M, sizeof(ib.M));
         ib.material = it->second.material; ib.motion = d3(0, 0, 0);
+        ib.obj = it->second.obj;
         insts.push_back(ib);
     }
+    S.object_inst.assign((size_t)std::max(0, d->num_objects), -1);
+    for (size_t i = 0; i < insts.size(); ++i)
+        if (insts[i].obj >= 0) S.object_inst[(size_t)insts[i].obj] = (int32_t)i;
 
     phase("flatten");
     // ---- BLAS builds (buildBLASForMesh: maxLeaf 2, SAH, 12 bins; RTContext.swift:430-435)
@@ -1380,6 +1410,8 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         ib.wlo[0] = mn.x; ib.wlo[1] = mn.y; ib.wlo[2] = mn.z;
         ib.whi[0] = mx.x; ib.whi[1] = mx.y; ib.whi[2] = mx.z;
         for (int k = 0; k < 3; ++k) { wlo[k] = std::fmin(wlo[k], ib.wlo[k]); whi[k] = std::fmax(whi[k], ib.whi[k]); }
+        S.inst_bounds.insert(S.inst_bounds.end(), ib.wlo, ib.wlo + 3);
+        S.inst_bounds.insert(S.inst_bounds.end(), ib.whi, ib.whi + 3);
         tp.bmin.insert(tp.bmin.end(), ib.wlo, ib.wlo + 3);
         tp.bmax.insert(tp.bmax.end(), ib.whi, ib.whi + 3);
         const D3 c = (d3(ib.wlo[0], ib.wlo[1], ib.wlo[2]) + d3(ib.whi[0], ib.whi[1], ib.whi[2])) * 0.5;
@@ -1432,6 +1464,10 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         S.tlas_root_ref = layout_bvh(tb, S.recs, emit);
         S.tlas_records = (int64_t)S.recs.size() - S.blas_records;
         S.has_tlas = true;
+        if (S.dynamic) {
+            S.dyn.tlas = tb;
+            S.dyn.tlas_recs.assign(S.recs.begin() + S.blas_records, S.recs.end());
+        }
         // Stack entries a walk can hold (device.h Stack, kStackCap): one deferred far child per
         // inner node on the current path, TLAS path below BLAS path (+2 slack).  The unified
         // identity walk also pushes a whole TLAS leaf's instance roots at once.
@@ -1456,7 +1492,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
     // and TLAS + BLAS records can be walked as one tree with one stack.  Each BLAS must
     // belong to exactly one instance so a triangle identifies its instance.
     {
-        bool ident = S.has_tlas;
+        bool ident = S.has_tlas && !S.dynamic;      // a dynamic scene keeps the transformed layout
         std::vector<int> owners(blases.size(), 0);
         for (size_t i = 0; i < insts.size() && ident; ++i) {
             const InstBuild& ib = insts[i];
@@ -1483,6 +1519,53 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
     if (S.identity) build_wide(S);
     else build_wide_tw(S);
     phase("wide");
+    if (S.dynamic) {
+        DynScene& Y = S.dyn;
+        Y.blas.resize(blases.size());
+        for (size_t b = 0; b < blases.size(); ++b) {
+            const BlasBuild& bb = blases[b];
+            DynBlas& y = Y.blas[b];
+            y.tri_first = bb.tri_first; y.tri_end = bb.tri_end; y.kind = bb.kind;
+            y.pmin[0] = bb.pmin.x; y.pmin[1] = bb.pmin.y; y.pmin[2] = bb.pmin.z;
+            y.pmax[0] = bb.pmax.x; y.pmax[1] = bb.pmax.y; y.pmax[2] = bb.pmax.z;
+            y.motion[0] = bb.motion.x; y.motion[1] = bb.motion.y; y.motion[2] = bb.motion.z;
+            y.P = blasP[b];
+        }
+        Y.inst_blas.resize(insts.size());
+        for (size_t i = 0; i < insts.size(); ++i) Y.inst_blas[i] = insts[i].blas;
+        if (!S.compact_tris) {                      // no CTri: the triangles' exact local boxes
+            Y.pbox.resize(6 * S.tris.size());
+            for (size_t q = 0; q < S.tris.size(); ++q) {
+                const Tri& t = triangles[S.tris[q].prim];
+                const D3 mn = vmin(t.v0, vmin(t.v1, t.v2)), mx = vmax(t.v0, vmax(t.v1, t.v2));
+                double* o = &Y.pbox[6 * q];
+                o[0] = mn.x; o[1] = mn.y; o[2] = mn.z; o[3] = mx.x; o[4] = mx.y; o[5] = mx.z;
+            }
+        }
+        // per-level node lists (octant copy 0), deepest level first
+        auto levels = [&](int32_t root, RefitLevels& L) {
+            L.nodes.clear(); L.off.clear();
+            if (root < 0 || S.wnodes.empty()) return;
+            std::vector<std::vector<int32_t>> lv{{root}};
+            for (;;) {
+                std::vector<int32_t> next;
+                for (int32_t n : lv.back()) {
+                    const W4Node& w = S.wnodes[(size_t)n];
+                    for (int c = 0; c < 4; ++c)
+                        if (w.pnear[0][c] < HUGE_VALF && w.ref[c] >= 0) next.push_back(w.ref[c]);
+                }
+                if (next.empty()) break;
+                lv.push_back(std::move(next));
+            }
+            for (size_t l = lv.size(); l-- > 0;) {
+                L.off.push_back((int64_t)L.nodes.size());
+                L.nodes.insert(L.nodes.end(), lv[l].begin(), lv[l].end());
+            }
+            L.off.push_back((int64_t)L.nodes.size());
+        };
+        levels(S.winst.empty() ? -1 : S.wide_root, Y.tlas_levels);
+        levels(S.fit_root, Y.fit_levels);
+    }
     if (trace && S.fit_root >= 0)
         std::fprintf(stderr, "[build] fit: %zu pairs, %lld nodes, depth %lld, coord %.6g, %.1f ms\n", S.fpairs.size(),
                      (long long)S.fit_nodes, (long long)S.fit_depth, S.fit_coord, S.fit_ms);
@@ -1497,6 +1580,130 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
     }
     phase("tlas+inst");
     S.build_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return RT_OK;
+}
+
+// ------------------------------------------------------------ dynamic scenes: refit (host part)
+bool matrix_ok(const double m[16]) {
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(m[k])) return false;
+    const double det = m3_det_of4(m);
+    return std::isfinite(det) && det != 0.0;
+}
+
+void set_instance_matrix(HostScene& S, int32_t k, const double m[16]) {   // makeInstance (RTContext.swift:437-457)
+    DInstance& di = S.insts[(size_t)k];
+    std::memcpy(di.l2w, m, sizeof(di.l2w));
+    m4_inverse(m, di.w2l);
+    normal_matrix(m, di.nmat);
+    di.det_neg = m3_det_of4(m) < 0.0 ? 1 : 0;
+}
+
+void special_instance_bounds(const HostScene& S, int32_t k, const double m[16], double lo[3], double hi[3]) {
+    const DynBlas& y = S.dyn.blas[(size_t)S.dyn.inst_blas[(size_t)k]];
+    aabb_transformed(y.pmin, y.pmax, m, lo, hi);
+}
+
+// refitTLAS (RTContext.swift:883-927) steps 2-4 and what this renderer derives from them.  The
+// TLAS keeps its topology and primIdx; a leaf's bounds are the min / max over its instances'
+// world bounds, an inner node's the union of its children's (BVHBuilder.refit, BVH.swift:254-291).
+int32_t refit_host_scene(HostScene& S, std::string& err) {
+    DynScene& Y = S.dyn;
+    const size_t n = S.insts.size();
+    if (!S.dynamic) { err = "not a dynamic scene"; return RT_ERR_UNSUPPORTED; }
+    if (!S.has_tlas || n == 0) return RT_OK;
+    RefBVH& tb = Y.tlas;
+    std::vector<int64_t> order, st{0};             // preorder: children come after their parent
+    while (!st.empty()) {
+        const int64_t i = st.back(); st.pop_back();
+        order.push_back(i);
+        if (!tb.isLeaf(i) && tb.nodesUsed > 0) { st.push_back(tb.leftFirst[i] + 1); st.push_back(tb.leftFirst[i]); }
+    }
+    for (size_t q = order.size(); q-- > 0;) {
+        const int64_t i = order[q];
+        double* lo = &tb.lo[3 * i];
+        double* hi = &tb.hi[3 * i];
+        if (tb.isLeaf(i) || tb.nodesUsed == 0) {
+            for (int k = 0; k < 3; ++k) { lo[k] = kInf; hi[k] = -kInf; }
+            for (int64_t p = 0; p < tb.count[i]; ++p) {
+                const double* b = &S.inst_bounds[6 * (size_t)tb.primIdx[tb.leftFirst[i] + p]];
+                for (int k = 0; k < 3; ++k) { lo[k] = std::fmin(lo[k], b[k]); hi[k] = std::fmax(hi[k], b[3 + k]); }
+            }
+            // DWideInst::tbox: the box of the TLAS leaf holding the instance (layout.h)
+            for (int64_t p = 0; p < tb.count[i] && !S.winst.empty(); ++p) {
+                double* t = S.winst[(size_t)tb.primIdx[tb.leftFirst[i] + p]].tbox;
+                for (int k = 0; k < 3; ++k) { t[k] = lo[k]; t[3 + k] = hi[k]; }
+            }
+        } else {
+            const int64_t L = tb.leftFirst[i], R = L + 1;
+            for (int k = 0; k < 3; ++k) {
+                lo[k] = std::fmin(tb.lo[3 * L + k], tb.lo[3 * R + k]);
+                hi[k] = std::fmax(tb.hi[3 * L + k], tb.hi[3 * R + k]);
+            }
+        }
+    }
+    for (int k = 0; k < 3; ++k) { S.tlas_root_lo[k] = tb.lo[k]; S.tlas_root_hi[k] = tb.hi[k]; }
+    {   // the TLAS records again, in the layout of the build (layout_bvh depends on the topology only)
+        std::vector<WRec> recs;
+        int64_t entries = 0;
+        auto emit = [&](int64_t, int64_t count) -> int64_t {
+            const int64_t first = S.tlas_leaf_base + entries;
+            entries += count;
+            return first;
+        };
+        const int32_t root = layout_bvh(tb, recs, emit);
+        for (WRec& r : recs)
+            for (int c = 0; c < 2; ++c)
+                if (r.ref[c] >= 0) r.ref[c] += (int32_t)S.blas_records;
+        const int32_t root_ref = root >= 0 ? root + (int32_t)S.blas_records : root;
+        if (root_ref != S.tlas_root_ref || recs.size() != Y.tlas_recs.size() || entries != (int64_t)S.tlas_leaf.size()) {
+            err = "TLAS layout changed under a refit";
+            return RT_ERR_INVALID_ARG;
+        }
+        for (size_t q = 0; q < recs.size(); ++q)
+            if (recs[q].ref[0] != Y.tlas_recs[q].ref[0] || recs[q].ref[1] != Y.tlas_recs[q].ref[1]) {
+                err = "TLAS layout changed under a refit";
+                return RT_ERR_INVALID_ARG;
+            }
+        Y.tlas_recs.swap(recs);
+    }
+    // the constants renders derive their margins from (build_host_scene, "pruning margin")
+    double wlo[3] = {kInf, kInf, kInf}, whi[3] = {-kInf, -kInf, -kInf};
+    double pruneK = 0.0, fitCoord = 0.0;
+    bool blocked = false;
+    for (size_t i = 0; i < n; ++i) {
+        const double* b = &S.inst_bounds[6 * i];
+        for (int k = 0; k < 3; ++k) { wlo[k] = std::fmin(wlo[k], b[k]); whi[k] = std::fmax(whi[k], b[3 + k]); }
+        const DInstance& di = S.insts[i];
+        double fro = 0.0;
+        for (int c = 0; c < 3; ++c)
+            for (int r = 0; r < 3; ++r) fro += di.w2l[c * 4 + r] * di.w2l[c * 4 + r];
+        pruneK = std::fmax(pruneK, Y.blas[(size_t)Y.inst_blas[i]].P * std::sqrt(fro));
+        if (!S.winst.empty()) {
+            const double nl = m3_inf_norm(di.l2w);
+            if (!(nl * m3_inf_norm(di.w2l) <= kFitKappa)) blocked = true;
+            const double t = std::fmax(std::fabs(di.l2w[12]), std::fmax(std::fabs(di.l2w[13]), std::fabs(di.l2w[14])));
+            fitCoord = std::fmax(fitCoord, nl * S.winst[i].bcoord + t);
+        }
+    }
+    const double dx = whi[0] - wlo[0], dy = whi[1] - wlo[1], dz = whi[2] - wlo[2];
+    S.scene_extent = std::sqrt(dx * dx + dy * dy + dz * dz);
+    if (!std::isfinite(S.scene_extent) || S.scene_extent <= 0) S.scene_extent = 1.0;
+    for (int k = 0; k < 3; ++k) S.scene_center[k] = 0.5 * (wlo[k] + whi[k]);
+    if (!std::isfinite(S.scene_center[0] + S.scene_center[1] + S.scene_center[2]))
+        S.scene_center[0] = S.scene_center[1] = S.scene_center[2] = 0.0;
+    S.prune_k = (S.eps > 0) ? 8.0 * std::ldexp(1.0, -53) * pruneK / S.eps : kInf;
+    S.det_scale = pruneK;
+    if (!S.winst.empty()) {
+        // every TLAS box lies inside the root's, so the largest |coordinate| is the root's
+        S.wide_coord = 0.0;
+        for (int k = 0; k < 3; ++k)
+            S.wide_coord = std::fmax(S.wide_coord, std::fmax(std::fabs(S.tlas_root_lo[k]), std::fabs(S.tlas_root_hi[k])));
+        // fit_coord after a refit: the host bound max over instances of |l2w|_inf * bcoord +
+        // |translation| (wide.h fit_walk header), with one part in 2^40 for its own rounding
+        if (S.fit_root >= 0) S.fit_coord = fitCoord * (1.0 + 0x1p-40);
+        Y.fit_blocked = blocked;
+    }
     return RT_OK;
 }
 

@@ -38,6 +38,35 @@ int64_t ref_bvh_depth(const RefBVH& b);   // max number of inner nodes on a root
 
 struct HostCamera { rt_camera c; };
 
+// ---- dynamic scenes (rt_scene_create_ex with RT_SCENE_DYNAMIC; scene.cpp refit_host_scene) -----
+// What a commit needs after the large host arrays are gone: per BLAS its TriRec run, kind, the
+// bounds of a sphere / plane, the motion vector and the pruning-margin constant; per instance its
+// BLAS; the TLAS in reference form (topology and primIdx are kept, bounds are refit bottom-up as
+// BVHBuilder.refit does, BVH.swift:254-291); and, for the four-wide TLAS nodes and the flattened
+// instance tree, the nodes of every level, deepest level first (the device refits a level per
+// launch, refit.h).
+struct DynBlas {
+    int64_t tri_first = 0, tri_end = 0;
+    int32_t kind = kPrimTriangles;
+    double pmin[3] = {0, 0, 0}, pmax[3] = {0, 0, 0};   // spheres / planes: the primitive's bounds
+    double motion[3] = {0, 0, 0};
+    double P = 0.0;                                    // pruning margin constant (scene.cpp blasP)
+};
+struct RefitLevels {
+    std::vector<int32_t> nodes;            // node indices (octant copy 0), deepest level first
+    std::vector<int64_t> off;              // level l is nodes[off[l], off[l + 1])
+};
+struct DynScene {
+    std::vector<DynBlas> blas;
+    std::vector<int32_t> inst_blas;
+    RefBVH tlas;
+    std::vector<WRec> tlas_recs;           // host image of the TLAS records (re-laid by a commit)
+    RefitLevels tlas_levels, fit_levels;
+    std::vector<double> pbox;              // 6 per TriRec: the triangle's exact local box (when the
+                                           // scene has no CTri; dropped after upload)
+    bool fit_blocked = false;              // an instance exceeds kFitKappa: tw_walk until a commit passes
+};
+
 struct HostScene {
     // ---- scene-level parameters
     double eps = 0, shadow_eps = 0;
@@ -66,6 +95,10 @@ struct HostScene {
     int64_t tlas_leaf_base = 0;            // TLAS leaf refs are ~(tlas_leaf_base + entry)
     bool has_tlas = false;
     bool identity = false;                 // all instances identity & static (unified walk)
+    bool dynamic = false;                  // set before build_host_scene: identity stays false, dyn is filled
+    DynScene dyn;
+    std::vector<double> inst_bounds;       // 6 per instance: Instance.worldBounds (lo, hi)
+    std::vector<int32_t> object_inst;      // per scene object: the instance it produced, or -1
     int64_t blas_records = 0, tlas_records = 0;
     int64_t max_stack = 0;                 // traversal stack entries the general walk needs
     int64_t max_stack_unified = 0;         // ... and the unified identity walk
@@ -102,6 +135,17 @@ struct HostScene {
 
 // Returns RT_OK or a negative status with `err` set.
 int32_t build_host_scene(const rt_scene_desc* desc, HostScene& out, std::string& err);
+
+// Dynamic scenes.  set_instance_matrix: instance k's DInstance fields that depend on localToWorld
+// (l2w, w2l, nmat, det_neg).  special_instance_bounds: world bounds of a sphere / plane instance
+// (one primitive: AABB.transformed of its box).  refit_host_scene: after inst_bounds and insts are
+// current, everything else a render derives from the transforms - the TLAS bounds bottom-up, the
+// TLAS records (dyn.tlas_recs), tlas_root_lo/hi, DWideInst::tbox, scene_extent / scene_center,
+// prune_k, det_scale, wide_coord, fit_coord and the kFitKappa check (dyn.fit_blocked).
+bool matrix_ok(const double m[16]);        // finite, upper 3x3 determinant finite and non-zero
+void set_instance_matrix(HostScene& S, int32_t k, const double m[16]);
+void special_instance_bounds(const HostScene& S, int32_t k, const double m[16], double lo[3], double hi[3]);
+int32_t refit_host_scene(HostScene& S, std::string& err);
 
 // PLY loading (ply.cpp).  Mirrors PLYLoader.load (RT/Helpers/PLYReader.swift:54-210).
 int32_t ply_load(const char* path, std::vector<double>& positions, std::vector<double>& normals,

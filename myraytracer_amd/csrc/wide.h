@@ -245,6 +245,22 @@ struct TwParked {
 // A candidate is accepted only after the exact FP64 tests of the three boxes, with the reference's
 // local ray (the same m4_point arithmetic as ut_walk); equal-t candidates raise `tie` and are
 // re-walked in the reference's order (ut_walk).  No local FP32 walk: local rays need no range.
+//
+// Dynamic scenes (rt_scene_commit; refit.h).  A commit keeps the topology of the TLAS's four-wide
+// nodes and of this tree and recomputes their boxes bottom-up: a pair's box from its leaf box and
+// the instance's new localToWorld (build_fit's formula), an instance marker's from its refit TLAS
+// leaf box, an inner slot's as the union of its child node's slots.  Every slot box still contains
+// its children's, so both trees remain superset filters and the argument above holds word for
+// word; the exact FP64 tests use the refit bounds the reference's own refitTLAS would hold
+// (RTContext.swift:883-927: TLAS leaf = min / max over its instances' world bounds, inner = union
+// of children).  Only the quality of the trees (overlap after large moves) depends on the pose
+// they were built at.  fit_coord after a refit is the host bound
+//   max over instances of ||l2w||_inf * bcoord + max |translation|   (scene.cpp refit_host_scene),
+// never smaller than the value build_fit computes exactly - each pair corner has local magnitude
+// <= bcoord, so its world image and the products nl * lc stay below the bound - and a larger R
+// only loosens the filter.  An instance whose transform exceeds kFitKappa blocks the fit walk
+// (renders take tw_walk) until a later commit passes; a scene built without this tree never
+// gets one.
 __device__ __forceinline__ bool fit_boxes_exact(const RenderParams& P, int k, int t0, const V3& o, const V3& d,
                                                 const V3& ol, const V3& dl) {
     const DWideInst& WI = P.winst[k];

@@ -113,16 +113,22 @@ class RenderProgress:                    # Models/RenderProgress.swift:8-14
 class RayTracerEngine:
     """Device-resident scene + renderer (one full replica per listed GPU)."""
 
-    def __init__(self, scene: Scene, devices: Optional[Sequence[int]] = None):
+    def __init__(self, scene: Scene, devices: Optional[Sequence[int]] = None, dynamic: bool = False):
+        """dynamic: instances and cameras may move between renders (set_transform / set_camera /
+        commit; rt_scene_create_ex with RT_SCENE_DYNAMIC)."""
         lib = load_library()
         self.scene = scene
         self._packed = scene.to_desc()
         handle = C.c_void_p()
         devs = list(devices) if devices else [0]
         arr = (C.c_int32 * len(devs))(*devs)
-        _check(lib.rt_scene_create(self._packed.ptr, arr, len(devs), C.byref(handle)))
+        if dynamic:
+            _check(lib.rt_scene_create_ex(self._packed.ptr, arr, len(devs), A.RT_SCENE_DYNAMIC, C.byref(handle)))
+        else:
+            _check(lib.rt_scene_create(self._packed.ptr, arr, len(devs), C.byref(handle)))
         self._h = handle
         self.devices = devs
+        self.dynamic = bool(dynamic)
 
     @classmethod
     def from_file(cls, path, format: str = "auto", devices: Optional[Sequence[int]] = None) -> "RayTracerEngine":
@@ -172,6 +178,46 @@ class RayTracerEngine:
         v = C.c_int64()
         _check(load_library().rt_scene_get_option(self._h, name.encode(), C.byref(v)))
         return int(v.value)
+
+    # -- dynamic scenes (RTContext.refitTLAS, RTContext.swift:883-927)
+    def instance_of(self, object_index: int) -> int:
+        """The instance scene object `object_index` produced (-1: none)."""
+        k = C.c_int32(-1)
+        _check(load_library().rt_scene_instance_of_object(self._h, int(object_index), C.byref(k)))
+        return int(k.value)
+
+    def set_transform(self, object_index: int, m16):
+        """Stage a new column-major localToWorld for the instance of scene object `object_index`
+        (applied by commit()); self.scene.objects[object_index].transform follows, so
+        oracle.OracleScene(self.scene) is the reference scene for the engine's next committed state."""
+        m = np.ascontiguousarray(np.asarray(m16, dtype=np.float64).reshape(-1))
+        if m.size != 16:
+            raise ValueError("a transform is 16 values, column-major")
+        k = self.instance_of(object_index) if self.dynamic else 0
+        if k < 0:
+            raise RenderError(A.RT_ERR_INVALID_ARG, f"object {object_index} produced no instance")
+        _check(load_library().rt_scene_set_instance_transform(self._h, k, m.ctypes.data_as(A.c_double_p)))
+        self.scene.objects[object_index].transform = tuple(float(x) for x in m)
+
+    def set_camera(self, index: int, camera):
+        """Replace camera `index` (takes effect at once); self.scene.cameras[index] follows."""
+        from .scene import pack_camera
+        cc = pack_camera(camera)
+        _check(load_library().rt_scene_set_camera(self._h, int(index), C.byref(cc)))
+        self.scene.cameras[index] = camera
+
+    def commit(self) -> A.rt_commit_stats:
+        """Apply the staged transforms (rt_scene_commit): blocks until every replica is updated."""
+        st = A.rt_commit_stats()
+        _check(load_library().rt_scene_commit(self._h, C.byref(st)))
+        return st
+
+    def instance_bounds(self, instance: int):
+        """Instance.worldBounds of an instance: (lo[3], hi[3]) float64 arrays."""
+        lo, hi = np.empty(3), np.empty(3)
+        _check(load_library().rt_scene_instance_bounds(self._h, int(instance), lo.ctypes.data_as(A.c_double_p),
+                                                       hi.ctypes.data_as(A.c_double_p)))
+        return lo, hi
 
     # -- introspection (RayTracer.swift:52-67)
     def info(self) -> A.rt_scene_info:

@@ -137,6 +137,21 @@ class MeshInstance:
 SceneObject = Union[Mesh, Triangle, Sphere, Plane, MeshInstance]
 
 
+def pack_camera(c: Camera) -> A.rt_camera:
+    """A Camera as the rt_camera of include/rtcore.h (rt_scene_desc.cameras, rt_scene_set_camera)."""
+    cc = A.rt_camera()
+    cc.type = A.RT_CAM_LOOKAT if (c.type or "").lower() == "lookat" else A.RT_CAM_NEARPLANE
+    cc.width, cc.height = int(c.image_resolution[0]), int(c.image_resolution[1])
+    cc.num_samples = int(c.num_samples)
+    cc.position, cc.gaze_point, cc.gaze, cc.up = _v(c.position), _v(c.gaze_point), _v(c.gaze), _v(c.up)
+    cc.fovy = float("nan") if c.fovy is None else float(c.fovy)
+    cc.near_distance = float(c.near_distance)
+    for k in range(4):
+        cc.near_plane[k] = float(c.near_plane[k])
+    cc.aperture_size, cc.focus_distance = float(c.aperture_size), float(c.focus_distance)
+    return cc
+
+
 @dataclass
 class Scene:
     cameras: List[Camera]
@@ -175,17 +190,7 @@ class PackedScene:
             als[i] = A.rt_area_light(_v(l.position), _v(l.normal), _v(l.radiance), float(l.size))
         cams = (A.rt_camera * max(1, len(s.cameras)))()
         for i, c in enumerate(s.cameras):
-            cc = A.rt_camera()
-            cc.type = A.RT_CAM_LOOKAT if (c.type or "").lower() == "lookat" else A.RT_CAM_NEARPLANE
-            cc.width, cc.height = int(c.image_resolution[0]), int(c.image_resolution[1])
-            cc.num_samples = int(c.num_samples)
-            cc.position, cc.gaze_point, cc.gaze, cc.up = _v(c.position), _v(c.gaze_point), _v(c.gaze), _v(c.up)
-            cc.fovy = float("nan") if c.fovy is None else float(c.fovy)
-            cc.near_distance = float(c.near_distance)
-            for k in range(4):
-                cc.near_plane[k] = float(c.near_plane[k])
-            cc.aperture_size, cc.focus_distance = float(c.aperture_size), float(c.focus_distance)
-            cams[i] = cc
+            cams[i] = pack_camera(c)
         objs = (A.rt_object * max(1, len(s.objects)))()
         base_material = {o.id: o.material for o in s.objects if isinstance(o, Mesh)}
         for i, o in enumerate(s.objects):
