@@ -429,6 +429,56 @@ int32_t  rt_debug_host_build(const rt_scene_desc* desc, uint64_t* hashes, int32_
  * out[4] = a hash of the pairs and the nodes (octant copy 0). */
 int32_t  rt_debug_fit_build(const rt_scene_desc* desc, int64_t* out);
 
+/* The four-wide trees themselves (wide.h: the identity tree, or the TLAS / per-BLAS trees and the
+ * flattened instance tree of a transformed scene), as plain copies, for the structural tests
+ * (tests/wide_tree_check.py).  Like every hook of this section the pair is not part of the
+ * versioned surface: it was added without moving RT_ABI_VERSION, as rt_debug_fit_build was.
+ *   rt_debug_wide_build   builds on the host like rt_debug_fit_build (no device is touched) with
+ *                         rt_scene_create_ex's flags, and copies from the host arrays before they
+ *                         are dropped.
+ *   rt_debug_wide_read    copies back from device replica `slot` after a device synchronisation
+ *                         (hipMemcpy, no kernel); RT_ERR_BUSY while a submitted render has not been
+ *                         waited for.
+ * Every call fills the counts and scalars.  A buffer pointer that is NULL is skipped; one that is
+ * not must hold what its count says, and the caller states what it allocated in the cap_* fields
+ * (RT_ERR_INVALID_ARG when a buffer is too small): call once with every pointer NULL, size the
+ * buffers, call again.  A scene without a four-wide tree reports wide_root = -1 and zero counts. */
+typedef struct rt_wide_dump {
+    /* ---- out: counts */
+    int64_t wnodes;           /* 128-byte node records over all eight octant copies (8 * wide_copy) */
+    int64_t wide_copy;        /* nodes per octant copy                                              */
+    int64_t tris;             /* TriRecs (lbox, tri_prim and tri_last have one entry per TriRec)    */
+    int64_t pairs;            /* (leaf run, instance) pairs of the flattened instance tree          */
+    int64_t instances;        /* instances (tbox, wroot and bcoord are zero for an identity tree)   */
+    int64_t tw_tlas_nodes;    /* nodes [0, this) of a copy are the TLAS's (transformed scenes)      */
+    int64_t fit_nodes;
+    int64_t marker_base;      /* terminal slot ~(marker_base + k) is instance k's marker            */
+    int64_t tlas_leaf_base;   /* terminal slots ~t with t below this are leaf runs                  */
+    /* ---- out: scalars */
+    int32_t wide_root, fit_root;          /* -1: none */
+    int32_t identity;                     /* the identity layout (build_wide) */
+    int32_t fit_blocked;
+    double  wide_coord, fit_coord;
+    /* ---- in: capacities of the buffers below, in the units of the counts above */
+    int64_t cap_wnodes, cap_tris, cap_pairs, cap_instances;
+    /* ---- out: caller-sized buffers (NULL = skipped) */
+    void*    nodes;           /* wnodes raw records: float near[3][4], int32 ref[4], float far[3][4], int32 pad[4] */
+    double*  lbox;            /* 6 per TriRec: the exact box of the leaf run that starts there      */
+    int32_t* fpairs;          /* 2 per pair: first TriRec of the run, instance                      */
+    double*  l2w;             /* 16 per instance, column-major                                      */
+    double*  tbox;            /* 6 per instance: DWideInst::tbox                                    */
+    int32_t* wroot;           /* per instance: DWideInst::wroot (< 0: a BLAS of one leaf run)       */
+    double*  bcoord;          /* per instance: DWideInst::bcoord                                    */
+    double*  inst_bounds;     /* 6 per instance: Instance.worldBounds                               */
+    int32_t* tri_prim;        /* per TriRec: the caller's triangle (index over the scene's meshes and
+                               * triangle objects in object order).  An identity scene's TriRec holds
+                               * its owning instance instead: rt_debug_wide_build still reports the
+                               * triangle, rt_debug_wide_read (the device's copy) the instance     */
+    uint8_t* tri_last;        /* per TriRec: 1 = last of its leaf run                               */
+} rt_wide_dump;
+int32_t rt_debug_wide_build(const rt_scene_desc* desc, uint32_t flags, rt_wide_dump* io);
+int32_t rt_debug_wide_read(rt_scene* scene, int32_t slot, rt_wide_dump* io);
+
 /* Explicit-ray queries on device `slot` through the render kernels' traversal (host
  * arrays, n rays; o/d: 3 doubles per ray).  rt_debug_trace_rays = intersectTLAS
  * (RTContext.swift:619-720) with tMin: out_t (+inf on a miss), world hit point, world

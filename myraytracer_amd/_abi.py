@@ -85,6 +85,21 @@ class rt_commit_stats(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+class rt_wide_dump(C.Structure):
+    """rt_debug_wide_build / rt_debug_wide_read (rtcore.h): counts and scalars out, capacities in,
+    caller-sized buffers."""
+    _fields_ = [("wnodes", C.c_int64), ("wide_copy", C.c_int64), ("tris", C.c_int64), ("pairs", C.c_int64),
+                ("instances", C.c_int64), ("tw_tlas_nodes", C.c_int64), ("fit_nodes", C.c_int64),
+                ("marker_base", C.c_int64), ("tlas_leaf_base", C.c_int64),
+                ("wide_root", C.c_int32), ("fit_root", C.c_int32), ("identity", C.c_int32),
+                ("fit_blocked", C.c_int32), ("wide_coord", C.c_double), ("fit_coord", C.c_double),
+                ("cap_wnodes", C.c_int64), ("cap_tris", C.c_int64), ("cap_pairs", C.c_int64),
+                ("cap_instances", C.c_int64),
+                ("nodes", C.c_void_p), ("lbox", c_double_p), ("fpairs", c_int32_p), ("l2w", c_double_p),
+                ("tbox", c_double_p), ("wroot", c_int32_p), ("bcoord", c_double_p), ("inst_bounds", c_double_p),
+                ("tri_prim", c_int32_p), ("tri_last", C.POINTER(C.c_uint8))]
+
+
 class rt_work_counters(C.Structure):
     _fields_ = [("records_fetched", C.c_int64), ("tri_tests", C.c_int64), ("normal_fetches", C.c_int64),
                 ("instance_entries", C.c_int64), ("pixels", C.c_int64),
@@ -139,7 +154,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_file_last_error", "rt_scene_file_destroy", "rt_scene_set_option", "rt_scene_get_option",
     "rt_scene_set_unsafe_option",
     "rt_scene_create_ex", "rt_scene_instance_of_object", "rt_scene_set_instance_transform", "rt_scene_set_camera",
-    "rt_scene_instance_bounds", "rt_scene_commit",
+    "rt_scene_instance_bounds", "rt_scene_commit", "rt_debug_wide_build", "rt_debug_wide_read",
 ]
 RT_ABI_VERSION = 5
 
@@ -214,6 +229,11 @@ def bind(lib: C.CDLL) -> C.CDLL:
     if hasattr(lib, "rt_debug_fit_build"):   # round 6 (an older build may be loaded for an A/B, MYRT_LIB)
         lib.rt_debug_fit_build.argtypes = [P(rt_scene_desc), P(C.c_int64)]
         lib.rt_debug_fit_build.restype = C.c_int32
+    if hasattr(lib, "rt_debug_wide_build"):   # the four-wide trees read back (an older build may be loaded, MYRT_LIB)
+        lib.rt_debug_wide_build.argtypes = [P(rt_scene_desc), C.c_uint32, P(rt_wide_dump)]
+        lib.rt_debug_wide_build.restype = C.c_int32
+        lib.rt_debug_wide_read.argtypes = [C.c_void_p, C.c_int32, P(rt_wide_dump)]
+        lib.rt_debug_wide_read.restype = C.c_int32
     lib.rt_debug_trace_rays.argtypes = [C.c_void_p, C.c_int32, C.c_int32, c_double_p, c_double_p, c_double_p,
                                         c_double_p, c_double_p, c_double_p, c_double_p, c_int32_p]
     lib.rt_debug_trace_rays.restype = C.c_int32

@@ -3478,6 +3478,139 @@ int32_t rt_debug_fit_build(const rt_scene_desc* desc, int64_t* out) {
     }
 }
 
+// ---- debug: the four-wide trees as plain copies (rtcore.h rt_wide_dump; tests/wide_tree_check.py).
+// `S` supplies the counts and scalars; the arrays come from the host scene before they are dropped
+// (rt_debug_wide_build) or from a replica (rt_debug_wide_read).
+namespace {
+struct WideArrays {
+    const W4Node* wnodes = nullptr;
+    const double* lbox = nullptr;
+    const DFitPair* fpairs = nullptr;
+    const DWideInst* winst = nullptr;       // null: identity tree
+    const DInstance* insts = nullptr;
+    const TriRec* tris = nullptr;           // one of tris / ctris
+    const CTri* ctris = nullptr;
+};
+}  // namespace
+static int32_t wide_dump_fill(const HostScene& S, const WideArrays& A, rt_wide_dump* io) {
+    const bool has = S.wide_root >= 0 && S.wide_copy > 0;
+    io->wnodes = has ? 8 * S.wide_copy : 0;
+    io->wide_copy = has ? S.wide_copy : 0;
+    io->tris = has ? S.tlas_leaf_base : 0;
+    io->pairs = has && S.fit_root >= 0 ? (int64_t)S.fpairs.size() : 0;
+    io->instances = has ? (int64_t)S.insts.size() : 0;
+    io->tw_tlas_nodes = has ? S.tw_tlas_nodes : 0;
+    io->fit_nodes = has && S.fit_root >= 0 ? S.fit_nodes : 0;
+    io->marker_base = S.tlas_leaf_base + (int64_t)S.tlas_leaf.size();
+    io->tlas_leaf_base = S.tlas_leaf_base;
+    io->wide_root = has ? S.wide_root : -1;
+    io->fit_root = has ? S.fit_root : -1;
+    io->identity = S.identity ? 1 : 0;
+    io->fit_blocked = S.dyn.fit_blocked ? 1 : 0;
+    io->wide_coord = S.wide_coord;
+    io->fit_coord = S.fit_coord;
+    if ((io->nodes && io->cap_wnodes < io->wnodes) ||
+        ((io->lbox || io->tri_prim || io->tri_last) && io->cap_tris < io->tris) ||
+        (io->fpairs && io->cap_pairs < io->pairs) ||
+        ((io->l2w || io->tbox || io->wroot || io->bcoord || io->inst_bounds) && io->cap_instances < io->instances))
+        return fail(RT_ERR_INVALID_ARG, "rt_wide_dump: a buffer is smaller than its count");
+    if (!has) return RT_OK;
+    if (io->nodes) std::memcpy(io->nodes, A.wnodes, (size_t)io->wnodes * sizeof(W4Node));
+    if (io->lbox) std::memcpy(io->lbox, A.lbox, (size_t)io->tris * 6 * sizeof(double));
+    if (io->fpairs && io->pairs > 0) std::memcpy(io->fpairs, A.fpairs, (size_t)io->pairs * sizeof(DFitPair));
+    for (int64_t k = 0; k < io->instances; ++k) {
+        if (io->l2w) std::memcpy(io->l2w + 16 * k, A.insts[k].l2w, 16 * sizeof(double));
+        if (io->tbox) for (int a = 0; a < 6; ++a) io->tbox[6 * k + a] = A.winst ? A.winst[k].tbox[a] : 0.0;
+        if (io->wroot) io->wroot[k] = A.winst ? A.winst[k].wroot : 0;
+        if (io->bcoord) io->bcoord[k] = A.winst ? A.winst[k].bcoord : 0.0;
+        if (io->inst_bounds) std::memcpy(io->inst_bounds + 6 * k, &S.inst_bounds[6 * (size_t)k], 6 * sizeof(double));
+    }
+    for (int64_t t = 0; t < io->tris && (io->tri_prim || io->tri_last); ++t) {
+        const int32_t prim = A.ctris ? A.ctris[t].prim : A.tris[t].prim;
+        if (io->tri_prim) io->tri_prim[t] = S.tri_src.empty() ? prim : S.tri_src[(size_t)t];
+        if (io->tri_last) io->tri_last[t] = (uint8_t)((A.ctris ? A.ctris[t].last : A.tris[t].last) != 0);
+    }
+    return RT_OK;
+}
+
+int32_t rt_debug_wide_build(const rt_scene_desc* desc, uint32_t flags, rt_wide_dump* io) {
+    if (!desc) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!io) return fail(RT_ERR_INVALID_ARG, "NULL argument");
+    if (flags & ~RT_SCENE_DYNAMIC) return fail(RT_ERR_INVALID_ARG, "unknown scene flags");
+    try {
+        HostScene S;
+        S.dynamic = (flags & RT_SCENE_DYNAMIC) != 0;
+        S.keep_tri_src = true;
+        std::string err;
+        const int32_t rc = build_host_scene(desc, S, err);
+        if (rc != RT_OK) return fail(rc, err);
+        WideArrays A;
+        A.wnodes = S.wnodes.data(); A.lbox = S.lbox.data(); A.fpairs = S.fpairs.data();
+        A.winst = S.winst.empty() ? nullptr : S.winst.data();
+        A.insts = S.insts.data(); A.tris = S.tris.data();
+        return wide_dump_fill(S, A, io);
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    } catch (const std::exception& e) {
+        return fail(RT_ERR_INVALID_ARG, e.what());
+    }
+}
+
+int32_t rt_debug_wide_read(rt_scene* s, int32_t slot, rt_wide_dump* io) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!io) return fail(RT_ERR_INVALID_ARG, "NULL argument");
+    if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
+    try {
+        const HostScene& S = s->host;
+        DeviceReplica& r = s->devs[slot];
+        HIP_TRY(hipSetDevice(r.device));
+        HIP_TRY(hipDeviceSynchronize());
+        const bool has = S.wide_root >= 0 && S.wide_copy > 0;
+        const size_t nn = has ? (size_t)(8 * S.wide_copy) : 0, nt = has ? (size_t)S.tlas_leaf_base : 0;
+        const size_t np = has && S.fit_root >= 0 ? S.fpairs.size() : 0, ni = has ? S.insts.size() : 0;
+        const bool bufs = io->nodes || io->lbox || io->fpairs || io->l2w || io->tbox || io->wroot || io->bcoord ||
+                          io->inst_bounds || io->tri_prim || io->tri_last;
+        std::vector<W4Node> wn;
+        std::vector<double> lb;
+        std::vector<DFitPair> fp;
+        std::vector<DWideInst> wi;
+        std::vector<DInstance> in;
+        std::vector<TriRec> tr;
+        std::vector<CTri> ct;
+        WideArrays A;
+        if (has && bufs) {
+            wn.resize(nn); lb.resize(6 * nt); fp.resize(np); in.resize(ni);
+            HIP_TRY(hipMemcpy(wn.data(), r.wnodes, nn * sizeof(W4Node), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(lb.data(), r.lbox, 6 * nt * sizeof(double), hipMemcpyDeviceToHost));
+            if (np) HIP_TRY(hipMemcpy(fp.data(), r.fpairs, np * sizeof(DFitPair), hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(in.data(), r.insts, ni * sizeof(DInstance), hipMemcpyDeviceToHost));
+            if (!S.winst.empty()) {
+                wi.resize(ni);
+                HIP_TRY(hipMemcpy(wi.data(), r.winst, ni * sizeof(DWideInst), hipMemcpyDeviceToHost));
+            }
+            if (S.compact_tris) {
+                ct.resize(nt);
+                HIP_TRY(hipMemcpy(ct.data(), r.ctris, nt * sizeof(CTri), hipMemcpyDeviceToHost));
+            } else {
+                tr.resize(nt);
+                HIP_TRY(hipMemcpy(tr.data(), r.tris, nt * sizeof(TriRec), hipMemcpyDeviceToHost));
+            }
+            A.wnodes = wn.data(); A.lbox = lb.data(); A.fpairs = fp.data();
+            A.winst = wi.empty() ? nullptr : wi.data();
+            A.insts = in.data();
+            A.tris = tr.empty() ? nullptr : tr.data();
+            A.ctris = ct.empty() ? nullptr : ct.data();
+        }
+        return wide_dump_fill(S, A, io);              // without buffers or a tree: the counts only
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    } catch (const std::exception& e) {
+        return fail(RT_ERR_INVALID_ARG, e.what());
+    }
+}
+
 // ---- debug: explicit rays through the render kernels' traversal
 static int32_t debug_rays(rt_scene* s, int32_t slot, int32_t n, const double* o, const double* d, const double* tl,
                           const double* time, double* out_t, double* out_p, double* out_n, int32_t* out_mat,

@@ -1507,6 +1507,8 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         ident &= S.max_stack_unified <= kStackCap;  // else the general walk (fewer entries)
         S.identity = ident;
         if (ident) {
+            if (S.keep_tri_src) S.tri_src.resize(S.tris.size());
+            for (size_t t = 0; t < S.tri_src.size(); ++t) S.tri_src[t] = S.tris[t].prim;
             for (size_t i = 0; i < insts.size(); ++i) {
                 const BlasBuild& bb = blases[insts[i].blas];
                 for (int64_t t = bb.tri_first; t < bb.tri_end; ++t) {

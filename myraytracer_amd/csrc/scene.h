@@ -129,6 +129,9 @@ struct HostScene {
     // ---- bookkeeping / debug
     int64_t n_meshes = 0, n_tris = 0, n_spheres = 0, n_planes = 0;
     std::vector<uint64_t> inst_bvh_hash;   // per instance: canonical hash of its BLAS
+    bool keep_tri_src = false;             // set before build_host_scene by rt_debug_wide_build only
+    std::vector<int32_t> tri_src;          // ... then, identity scenes: per TriRec the reference `triangles[]`
+                                           // index its prim held before it became the owning instance
     uint64_t tlas_hash = 0;
     double build_ms = 0;
 };

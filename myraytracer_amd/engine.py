@@ -452,6 +452,46 @@ class RayTracerEngine:
     def bvh_hash(self, instance: int) -> int:
         return int(load_library().rt_debug_bvh_hash(self._h, instance))
 
+    def wide_read(self, slot: int = 0) -> dict:
+        """The four-wide trees of replica `slot`, copied back from the device (rt_debug_wide_read);
+        the dict of wide_build()."""
+        lib = load_library()
+        return _wide_dump(lambda io: lib.rt_debug_wide_read(self._h, int(slot), C.byref(io)))
+
+
+_WIDE_SCALARS = ("wnodes", "wide_copy", "tris", "pairs", "instances", "tw_tlas_nodes", "fit_nodes", "marker_base",
+                 "tlas_leaf_base", "wide_root", "fit_root", "identity", "fit_blocked", "wide_coord", "fit_coord")
+
+
+def _wide_dump(call) -> dict:
+    """Two calls of an rt_wide_dump hook: the counts, then the buffers sized from them.  Returns
+    the scalars under their rtcore.h names and the arrays: nodes (wnodes, 32) uint32 raw words of
+    the 128-byte records, lbox (tris, 6), fpairs (pairs, 2), l2w (instances, 16), tbox
+    (instances, 6), wroot, bcoord, inst_bounds (instances, 6), tri_prim, tri_last."""
+    io = A.rt_wide_dump()
+    _check(call(io))
+    nn, nt, npair, ni = int(io.wnodes), int(io.tris), int(io.pairs), int(io.instances)
+    arr = {"nodes": np.zeros((nn, 32), np.uint32), "lbox": np.zeros((nt, 6)), "fpairs": np.zeros((npair, 2), np.int32),
+           "l2w": np.zeros((ni, 16)), "tbox": np.zeros((ni, 6)), "wroot": np.zeros(ni, np.int32),
+           "bcoord": np.zeros(ni), "inst_bounds": np.zeros((ni, 6)), "tri_prim": np.zeros(nt, np.int32),
+           "tri_last": np.zeros(nt, np.uint8)}
+    io.cap_wnodes, io.cap_tris, io.cap_pairs, io.cap_instances = nn, nt, npair, ni
+    for name, a in arr.items():
+        if a.size:
+            setattr(io, name, a.ctypes.data_as(dict(A.rt_wide_dump._fields_)[name]))
+    _check(call(io))
+    assert (int(io.wnodes), int(io.tris), int(io.pairs), int(io.instances)) == (nn, nt, npair, ni)
+    out = {k: getattr(io, k) for k in _WIDE_SCALARS}
+    out.update(arr)
+    return out
+
+
+def wide_build(scene: Scene, dynamic: bool = False) -> dict:
+    """The four-wide trees of a host-only build (rt_debug_wide_build; no device is touched)."""
+    lib = load_library()
+    pk = scene.to_desc()
+    return _wide_dump(lambda io: lib.rt_debug_wide_build(pk.ptr, A.RT_SCENE_DYNAMIC if dynamic else 0, C.byref(io)))
+
 
 def _stats(st: A.rt_stats) -> RenderStats:
     return RenderStats(int(st.meshes), int(st.triangles), int(st.spheres), int(st.planes),

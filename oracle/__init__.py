@@ -51,7 +51,9 @@ def lib() -> C.CDLL:
         L.oracle_bvh_hash.restype = C.c_uint64
         L.oracle_num_instances.argtypes = [C.c_void_p]
         L.oracle_num_instances.restype = C.c_int32
-        L.oracle_pcg32_stream.argtypes = [C.c_uint64, C.c_int32, C.POINTER(C.c_uint32)]
+        L.oracle_tlas_leaves.argtypes = [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]
+        L.oracle_tlas_leaves.restype = C.c_int32
+        L.oracle_pcg32_stream.argtypes =[C.c_uint64, C.c_int32, C.POINTER(C.c_uint32)]
         L.oracle_pcg32_stream.restype = None
         d3 = C.POINTER(C.c_double)
         L.oracle_hit_aabb.argtypes = [d3, d3, d3, d3, C.c_double]
@@ -114,6 +116,13 @@ class OracleScene:
 
     def num_instances(self):
         return int(lib().oracle_num_instances(self._h))
+
+    def tlas_leaves(self):
+        """Per instance the id of the TLAS leaf that holds it (int32 array)."""
+        n = self.num_instances()
+        out = np.full(n, -1, np.int32)
+        lib().oracle_tlas_leaves(self._h, out.ctypes.data_as(C.POINTER(C.c_int32)), n)
+        return out
 
     @staticmethod
     def _rays(origins, dirs, tlim, time):

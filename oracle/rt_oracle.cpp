@@ -1276,6 +1276,32 @@ uint64_t oracle_bvh_hash(void* scene, int32_t instance) {
     return h;
 }
 
+// TLAS leaf membership (tests/wide_tree_check.py): leaf_of[instance] = the node index of the TLAS
+// leaf that holds it, for the first n instances.  Returns the number of TLAS leaves.
+int32_t oracle_tlas_leaves(void* scene, int32_t* leaf_of, int32_t n) {
+    using namespace orc;
+    const Context& C = static_cast<OracleScene*>(scene)->C;
+    const BVHBuilder& T = C.tlasBuilder;
+    if (C.instances.empty() || T.bvhNode.empty()) return 0;
+    int32_t leaves = 0;
+    std::vector<uint64_t> st{T.rootNodeIdx};
+    while (!st.empty()) {
+        const uint64_t i = st.back(); st.pop_back();
+        const BVHNode& node = T.bvhNode[i];
+        if (node.isLeaf()) {
+            ++leaves;
+            for (uint64_t q = 0; q < node.primitiveCount; ++q) {
+                const int64_t k = T.primitives[T.primitiveIdx[node.leftFirst + q]].primitiveIndex;
+                if (leaf_of && k >= 0 && k < n) leaf_of[k] = (int32_t)i;
+            }
+        } else {
+            st.push_back(node.leftFirst + 1);
+            st.push_back(node.leftFirst);
+        }
+    }
+    return leaves;
+}
+
 int32_t oracle_num_instances(void* scene) {
     return (int32_t) static_cast<orc::OracleScene*>(scene)->C.instances.size();
 }

@@ -33,14 +33,15 @@ def test_library_exports_every_declared_symbol():
 
 
 STRUCTS = ["rt_vec3", "rt_material", "rt_point_light", "rt_area_light", "rt_camera", "rt_object", "rt_scene_desc",
-           "rt_stats", "rt_scene_info", "rt_work_counters", "rt_ply_mesh"]
+           "rt_stats", "rt_scene_info", "rt_work_counters", "rt_ply_mesh", "rt_wide_dump"]
 
 
 def test_ctypes_layout_matches_header(tmp_path):
     prog = tmp_path / "sizes.c"
     body = "\n".join(f'printf("{s} %zu\\n", sizeof({s}));' for s in STRUCTS)
     offs = [("rt_object", f) for f, _ in A.rt_object._fields_] + [("rt_scene_desc", f) for f, _ in A.rt_scene_desc._fields_] + \
-           [("rt_camera", f) for f, _ in A.rt_camera._fields_]
+           [("rt_camera", f) for f, _ in A.rt_camera._fields_] + \
+           [("rt_wide_dump", f) for f, _ in A.rt_wide_dump._fields_]
     body += "\n" + "\n".join(f'printf("{s}.{f} %zu\\n", offsetof({s}, {f}));' for s, f in offs)
     prog.write_text(f'#include <stdio.h>\n#include <stddef.h>\n#include "{HEADER}"\nint main(void){{\n{body}\nreturn 0;}}\n')
     exe = tmp_path / "sizes"

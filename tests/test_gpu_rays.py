@@ -169,14 +169,10 @@ def _rotation(rng):
                      [2 * (x * z - y * w), 2 * (y * z + x * w), 1 - 2 * (x * x + y * y)]])
 
 
-@pytest.mark.parametrize("walk", ["wide", "unified", "general"])
-def test_near_degenerate_grazing_hits_and_the_pruning_margin(walk):
-    """Large, nearly coplanar triangles and rays grazing them through a corner (|det| just
-    above eps): Moeller-Trumbore's t then carries an error of up to ~1e-4 relative and can
-    undercut the entry distance of the triangle's own box - far beyond the round-1 margin
-    (1e-7 rel + 1e-9 diag), measured on CPU.  The margin now bounds that error
-    (scene.cpp, "pruning margin"), so pruning still never drops a node whose triangle the
-    reference would accept: hits stay bit-identical to the unpruned oracle."""
+def _grazing_set(n_rays=6000):
+    """Large, nearly coplanar triangles (one mesh) and rays grazing them through a corner (|det|
+    just above eps).  Returns the mesh, the rays and the generator (also used, mapped through an
+    instance's transform, by tests/test_gpu_refit_edges.py)."""
     rng = np.random.default_rng(17)
     R0 = _rotation(rng)
     V, F, corners = [], [], []
@@ -192,10 +188,8 @@ def test_near_degenerate_grazing_hits_and_the_pruning_margin(walk):
         corners.append((v0, e1, e2, Rk @ np.array([0.0, 0.0, 1.0])))
     mesh = M.Mesh(id=1, material="1", positions=np.array(V), indices=np.array(F, np.int32),
                   indices_one_based=False, shading_mode="flat")
-    sc = scenes.scaled(scenes.scene_c1(8, 8), 8, 8)
-    sc.objects = [mesh]
     O, D = [], []
-    for i in range(6000):
+    for i in range(n_rays):
         v0, e1, e2, nrm = corners[rng.integers(len(corners))]
         tgt = v0 + rng.uniform(0, 1e-9) * e1 + rng.uniform(0, 1e-9) * e2
         inplane = (e1 + e2) / np.linalg.norm(e1 + e2) + rng.uniform(-0.1, 0.1) * e1 / np.linalg.norm(e1)
@@ -204,7 +198,20 @@ def test_near_degenerate_grazing_hits_and_the_pruning_margin(walk):
         d /= np.linalg.norm(d)
         O.append(tgt - d * 10 ** rng.uniform(0, 3))
         D.append(d)
-    O, D = np.array(O), np.array(D)
+    return mesh, np.array(O), np.array(D), rng
+
+
+@pytest.mark.parametrize("walk", ["wide", "unified", "general"])
+def test_near_degenerate_grazing_hits_and_the_pruning_margin(walk):
+    """Large, nearly coplanar triangles and rays grazing them through a corner (|det| just
+    above eps): Moeller-Trumbore's t then carries an error of up to ~1e-4 relative and can
+    undercut the entry distance of the triangle's own box - far beyond the round-1 margin
+    (1e-7 rel + 1e-9 diag), measured on CPU.  The margin now bounds that error
+    (scene.cpp, "pruning margin"), so pruning still never drops a node whose triangle the
+    reference would accept: hits stay bit-identical to the unpruned oracle."""
+    mesh, O, D, rng = _grazing_set()
+    sc = scenes.scaled(scenes.scene_c1(8, 8), 8, 8)
+    sc.objects = [mesh]
     hit = _check_closest(sc, O, D, walk=walk)
     assert hit.mean() > 0.3
     t, *_ = oracle.OracleScene(sc).trace_rays(O, D)
