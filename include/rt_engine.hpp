@@ -102,11 +102,11 @@ public:
      * every listed device (empty = device 0).  The descriptor is copied.  dynamic: instances and
      * cameras may move between renders (setTransform / setCamera / commit; RT_SCENE_DYNAMIC). */
     explicit RayTracerEngine(const rt_scene_desc& desc, std::vector<int32_t> devices = {},
-                             std::vector<CameraMeta> cameraMeta = {}, bool dynamic = false)
+                             std::vector<CameraMeta> cameraMeta = {}, bool dynamic = false, bool deformable = false)
         : meta_(std::move(cameraMeta)) {
         for (int32_t i = 0; i < desc.num_cameras; ++i) cams_.push_back(desc.cameras[i]);
         check(rt_scene_create_ex(&desc, devices.empty() ? nullptr : devices.data(), (int32_t)devices.size(),
-                                 dynamic ? RT_SCENE_DYNAMIC : 0u, &scene_));
+                                 (dynamic ? RT_SCENE_DYNAMIC : 0u) | (deformable ? RT_SCENE_DEFORMABLE : 0u), &scene_));
     }
     /* RayTracerEngine.init(from: url) / init(data:) (RayTracer.swift:30-49): the scene file is
      * decoded by rt_scene_file_* (JSON or XML, ParsingKit's conventions), then built like the
@@ -171,6 +171,26 @@ public:
     rt_commit_stats commit() {
         rt_commit_stats st{};
         check(rt_scene_commit(scene_, &st));
+        return st;
+    }
+    /* Deforming meshes (an engine built with `deformable`, which implies `dynamic`): BVHBuilder.refit
+     * (BVH.swift:254-291) applied to a BLAS on the device.  setPositions stages xyz triples (and, for a
+     * mesh created with per-vertex normals, optionally new normals) for mesh object `objectIndex`
+     * until commit(); with RT_POSITIONS_DEVICE in `flags` the pointers are device pointers used in
+     * place, which must stay unchanged until commit() returns.  The caller keeps its own copy of the
+     * scene description up to date. */
+    int64_t vertexCount(int32_t objectIndex) const {
+        int64_t n = 0;
+        check(rt_scene_mesh_vertex_count(scene_, objectIndex, &n));
+        return n;
+    }
+    void setPositions(int32_t objectIndex, const double* positions, int64_t numPositions,
+                      const double* normals = nullptr, uint32_t flags = 0u) {
+        check(rt_scene_set_mesh_positions(scene_, objectIndex, positions, numPositions, normals, flags));
+    }
+    rt_deform_stats lastDeformStats() const {
+        rt_deform_stats st{};
+        check(rt_scene_last_deform_stats(scene_, &st));
         return st;
     }
     /* Instance.worldBounds of an instance (any scene), as of the last commit. */

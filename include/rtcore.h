@@ -52,7 +52,10 @@
  *      rt_scene_set_unsafe_option; rt_scene_set_option refuses them.
  *   5: dynamic scenes (appended, nothing existing changed): rt_scene_create_ex with
  *      RT_SCENE_DYNAMIC, rt_scene_instance_of_object, rt_scene_set_instance_transform,
- *      rt_scene_set_camera, rt_scene_instance_bounds, rt_scene_commit. */
+ *      rt_scene_set_camera, rt_scene_instance_bounds, rt_scene_commit.
+ *      Appended later without moving the version, as the rt_debug_wide_* pair was (callers detect
+ *      them by symbol): deforming meshes - RT_SCENE_DEFORMABLE, rt_scene_mesh_vertex_count,
+ *      rt_scene_set_mesh_positions, rt_scene_last_deform_stats. */
 #define RT_ABI_VERSION 5
 
 #ifdef __cplusplus
@@ -207,7 +210,8 @@ int32_t rt_scene_info_get(const rt_scene* scene, rt_scene_info* out);
  * rt_scene_commit then brings every acceleration structure up to date with the reference's refit
  * semantics: the TLAS keeps its topology and its bounds are recomputed bottom-up from the
  * instances' new world bounds.  No PLY is parsed again and no BLAS rebuilt.  Instances can not
- * be added or removed, and vertices do not move.  A dynamic scene always uses the transformed
+ * be added or removed; vertices move only in a scene created with RT_SCENE_DEFORMABLE as well
+ * ("deforming meshes" below).  A dynamic scene always uses the transformed
  * layout (also while every matrix is the identity); scenes created without the flag behave
  * exactly as before.
  *   rt_scene_create_ex               rt_scene_create with flags (rt_scene_create == flags 0).
@@ -245,6 +249,54 @@ typedef struct rt_commit_stats {
     double  total_ms;
 } rt_commit_stats;
 int32_t rt_scene_commit(rt_scene* scene, rt_commit_stats* stats /* may be NULL */);
+
+/* ---- deforming meshes (appended under ABI 5; detect by symbol) ---------------------------------
+ * BVHBuilder.refit(using:) (RayTracer/Accelearion/BVH.swift:254-291, "bottom-up AABB update")
+ * applied to a BLAS: a scene created with RT_SCENE_DEFORMABLE (which implies RT_SCENE_DYNAMIC)
+ * accepts new vertex positions for its meshes (skinning, cloth, morph targets) between renders.
+ * rt_scene_commit then rewrites the mesh's triangles, normals and boxes on the device and refits
+ * its BLAS with the topology kept (myraytracer_amd/csrc/deform.h): no rt_scene_create, no host
+ * round trip for positions that already live on the device.  Every instance of the mesh (the base
+ * mesh and every MeshInstance of it) follows.  A deformable scene keeps the FP64 layouts
+ * (compact_records / compact_tris are not used); scenes without the flag behave exactly as before.
+ *   rt_scene_mesh_vertex_count   the vertex count of RT_OBJ_MESH object `object_index` (inline
+ *                                num_positions, or the PLY's).
+ *   rt_scene_set_mesh_positions  stages xyz triples for that mesh until the next commit; renders
+ *       before the commit see the old pose, and staging is legal while renders are in flight.  A
+ *       second call for the same mesh replaces the first.  A host array is copied at the call.  With
+ *       RT_POSITIONS_DEVICE `positions` (and `normals`) are device pointers used in place: they must
+ *       stay valid and unchanged until the commit returns, and every replica of the scene must be on
+ *       the device that owns them (else RT_ERR_UNSUPPORTED).  RT_ERR_UNSUPPORTED without
+ *       RT_SCENE_DEFORMABLE.  RT_ERR_INVALID_ARG for an object that is not a mesh with at least one
+ *       triangle (another kind, an empty mesh, a PLY that failed to load) or a num_positions that is
+ *       not the mesh's vertex count.
+ *       Normals: a mesh created with per-vertex normals (inline or from its PLY) keeps them when
+ *       `normals` is NULL and takes the new ones (same count) otherwise.  A mesh created without
+ *       them derives flat or smooth normals from the new positions exactly as the build does;
+ *       non-NULL `normals` for such a mesh is RT_ERR_INVALID_ARG.
+ *   rt_scene_commit              applies staged positions and staged transforms together.  Before it
+ *       changes anything it checks every staged position array on the device - the whole array, so a
+ *       NaN in a vertex no triangle references is refused too: every value must be finite, and for
+ *       every instance of the mesh reach * (3 * c + 1) < 1e30 must hold (reach: the largest |entry| of
+ *       its staged or current matrix; c: the largest |coordinate| plus the largest |motionBlur|
+ *       component).  On failure: RT_ERR_INVALID_ARG, everything staged is dropped, nothing changed.
+ *   rt_scene_last_deform_stats   what the last rt_scene_commit did for deformations (zeros when it
+ *                                had none staged).  rt_commit_stats keeps its meaning; its total_ms
+ *                                includes this work.
+ * After a deformation rt_debug_bvh_hash still reports the build's hash. */
+#define RT_SCENE_DEFORMABLE 2u      /* rt_scene_create_ex flag; implies RT_SCENE_DYNAMIC */
+#define RT_POSITIONS_DEVICE 1u      /* positions / normals are device pointers */
+int32_t rt_scene_mesh_vertex_count(const rt_scene* scene, int32_t object_index, int64_t* num_positions);
+int32_t rt_scene_set_mesh_positions(rt_scene* scene, int32_t object_index,
+                                    const double* positions, int64_t num_positions,
+                                    const double* normals /* may be NULL */, uint32_t flags);
+typedef struct rt_deform_stats {
+    int64_t meshes_deformed, triangles, instances_rebounded;
+    double validate_ms;         /* staging copies to the device + the position check    */
+    double deform_ms;           /* triangles, triangle boxes, normals, leaf boxes       */
+    double blas_refit_ms;       /* BLAS records, four-wide BLAS nodes, root box read-back */
+} rt_deform_stats;
+int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);   /* of the last commit */
 
 /* Render options: tuning and test switches, each default being the production setting.
  *   wide (1)             conservative FP32 four-wide walk of identity scenes (exact: wide.h)

@@ -85,6 +85,15 @@ class rt_commit_stats(C.Structure):
                 ("total_ms", C.c_double)]
 
 
+RT_SCENE_DEFORMABLE = 2          # rt_scene_create_ex flag; implies RT_SCENE_DYNAMIC
+RT_POSITIONS_DEVICE = 1          # rt_scene_set_mesh_positions: positions / normals are device pointers
+
+
+class rt_deform_stats(C.Structure):
+    _fields_ = [("meshes_deformed", C.c_int64), ("triangles", C.c_int64), ("instances_rebounded", C.c_int64),
+                ("validate_ms", C.c_double), ("deform_ms", C.c_double), ("blas_refit_ms", C.c_double)]
+
+
 class rt_wide_dump(C.Structure):
     """rt_debug_wide_build / rt_debug_wide_read (rtcore.h): counts and scalars out, capacities in,
     caller-sized buffers."""
@@ -155,6 +164,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_set_unsafe_option",
     "rt_scene_create_ex", "rt_scene_instance_of_object", "rt_scene_set_instance_transform", "rt_scene_set_camera",
     "rt_scene_instance_bounds", "rt_scene_commit", "rt_debug_wide_build", "rt_debug_wide_read",
+    "rt_scene_mesh_vertex_count", "rt_scene_set_mesh_positions", "rt_scene_last_deform_stats",
 ]
 RT_ABI_VERSION = 5
 
@@ -261,4 +271,11 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.rt_scene_instance_bounds.restype = C.c_int32
         lib.rt_scene_commit.argtypes = [C.c_void_p, P(rt_commit_stats)]
         lib.rt_scene_commit.restype = C.c_int32
+    if hasattr(lib, "rt_scene_set_mesh_positions"):   # deforming meshes (appended under ABI 5: detected by symbol)
+        lib.rt_scene_mesh_vertex_count.argtypes = [C.c_void_p, C.c_int32, P(C.c_int64)]
+        lib.rt_scene_mesh_vertex_count.restype = C.c_int32
+        lib.rt_scene_set_mesh_positions.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_uint32]
+        lib.rt_scene_set_mesh_positions.restype = C.c_int32
+        lib.rt_scene_last_deform_stats.argtypes = [C.c_void_p, P(rt_deform_stats)]
+        lib.rt_scene_last_deform_stats.restype = C.c_int32
     return lib

@@ -159,24 +159,30 @@ struct RefitTree {
     const DInstance* insts;
 };
 
+// An empty slot has +inf planes; an inner slot takes the float union of its child node's slots
+// (shared with deform.h k_refit_blas_level)
+__device__ __forceinline__ bool refit_slot_empty(const W4Node& n, int c) { return !(n.pnear[0][c] < HUGE_VALF); }
+__device__ __forceinline__ void refit_slot_union(const W4Node& ch, float lo[3], float hi[3]) {
+    for (int k = 0; k < 3; ++k) { lo[k] = HUGE_VALF; hi[k] = -HUGE_VALF; }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) {
+        if (refit_slot_empty(ch, s)) continue;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], ch.pnear[k][s]); hi[k] = fmaxf(hi[k], ch.pfar[k][s]); }
+    }
+}
+
 // One thread per slot of the level's nodes.
 __global__ __launch_bounds__(256) void k_refit_level(RefitTree T) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= 4 * (int64_t)T.count) return;
     W4Node& n = T.nodes[T.list[i >> 2]];
     const int c = (int)(i & 3);
-    if (!(n.pnear[0][c] < HUGE_VALF)) return;                 // empty slot
+    if (refit_slot_empty(n, c)) return;
     const int32_t ref = n.ref[c];
     float lo[3], hi[3];
     if (ref >= 0) {                                           // union of the child node's slots
-        const W4Node& ch = T.nodes[ref];
-        for (int k = 0; k < 3; ++k) { lo[k] = HUGE_VALF; hi[k] = -HUGE_VALF; }
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            if (!(ch.pnear[0][s] < HUGE_VALF)) continue;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { lo[k] = fminf(lo[k], ch.pnear[k][s]); hi[k] = fmaxf(hi[k], ch.pfar[k][s]); }
-        }
+        refit_slot_union(T.nodes[ref], lo, hi);
     } else if (T.marker_base >= 0) {                          // instance marker: its TLAS leaf's box
         const double* b = T.winst[~ref - T.marker_base].tbox;
         for (int k = 0; k < 3; ++k) { lo[k] = refit_down(b[k]); hi[k] = refit_up(b[3 + k]); }

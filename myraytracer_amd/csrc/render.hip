@@ -32,6 +32,7 @@
 #include "layout.h"
 #include "refit.h"
 #include "scene.h"
+#include "deform.h"
 
 namespace myrt {
 namespace dev {
@@ -1352,6 +1353,19 @@ struct DeviceReplica {
     int32_t* fit_levels = nullptr;
     dev::RefitMove* moves = nullptr; double* bounds_part = nullptr; double* bounds_out = nullptr;
     int64_t moves_cap = 0, bounds_part_cap = 0;
+    // deformable scenes (deform.h): per TriRec its vertex ids, the BLAS records and four-wide nodes by
+    // level, the vertex adjacency of derived smooth normals; and scratch grown by a commit: the staged
+    // host arrays' device copies, unit face normals and vertex normals of one mesh, the reductions
+    int32_t* vid = nullptr;
+    int32_t* rec_list = nullptr;
+    int32_t* wide_list = nullptr;
+    int32_t* csr_off = nullptr;
+    int32_t* csr_tri = nullptr;
+    double* def_stage = nullptr; int64_t def_stage_cap = 0;
+    double* def_face = nullptr; int64_t def_face_cap = 0;
+    double* def_vnorm = nullptr; int64_t def_vnorm_cap = 0;
+    double* def_part = nullptr; int64_t def_part_cap = 0;
+    double* def_out = nullptr; int64_t def_out_cap = 0;
 };
 
 }  // namespace
@@ -1418,6 +1432,16 @@ struct rt_scene {
     int64_t next_ticket = 0;
     // dynamic scenes: transforms staged by rt_scene_set_instance_transform until rt_scene_commit
     std::vector<std::pair<int32_t, std::array<double, 16>>> staged;
+    // deformable scenes: positions staged by rt_scene_set_mesh_positions until rt_scene_commit (a host
+    // array is copied, a device array is used in place), and the figures of the last commit
+    struct StagedDeform {
+        int32_t blas = -1;
+        std::vector<double> pos, nrm;                 // host copies (empty with RT_POSITIONS_DEVICE)
+        const double* dpos = nullptr; const double* dnrm = nullptr;
+        bool has_nrm = false;
+    };
+    std::vector<StagedDeform> staged_deform;
+    rt_deform_stats last_deform{};
 };
 
 static int64_t full_scratch_bytes(const FullScratch& f) {
@@ -1506,6 +1530,9 @@ static void free_replica(DeviceReplica& r) {
     (void)hipFree(r.deep);
     (void)hipFree(r.pbox); (void)hipFree(r.tlas_levels); (void)hipFree(r.fit_levels);
     (void)hipFree(r.moves); (void)hipFree(r.bounds_part); (void)hipFree(r.bounds_out);
+    (void)hipFree(r.vid); (void)hipFree(r.rec_list); (void)hipFree(r.wide_list); (void)hipFree(r.csr_off); (void)hipFree(r.csr_tri);
+    (void)hipFree(r.def_stage); (void)hipFree(r.def_face); (void)hipFree(r.def_vnorm); (void)hipFree(r.def_part);
+    (void)hipFree(r.def_out);
     r.full.release();
     r.dev_full.release();
     (void)hipFree(r.arena.base);
@@ -1601,6 +1628,13 @@ static int32_t make_replica(const HostScene& S, int device, DeviceReplica& r, co
         if (!S.dyn.pbox.empty() && (rc = upload(S.dyn.pbox, &r.pbox, r.bytes)) != RT_OK) return rc;
         if ((rc = upload(S.dyn.tlas_levels.nodes, &r.tlas_levels, r.bytes)) != RT_OK) return rc;
         if ((rc = upload(S.dyn.fit_levels.nodes, &r.fit_levels, r.bytes)) != RT_OK) return rc;
+    }
+    if (S.deformable) {
+        if ((rc = upload(S.def.vid, &r.vid, r.bytes)) != RT_OK) return rc;
+        if ((rc = upload(S.def.rec_list, &r.rec_list, r.bytes)) != RT_OK) return rc;
+        if ((rc = upload(S.def.wide_list, &r.wide_list, r.bytes)) != RT_OK) return rc;
+        if ((rc = upload(S.def.csr_off, &r.csr_off, r.bytes)) != RT_OK) return rc;
+        if ((rc = upload(S.def.csr_tri, &r.csr_tri, r.bytes)) != RT_OK) return rc;
     }
     HIP_TRY(hipMalloc((void**)&r.counters, kCounterWords * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(r.counters, 0, kCounterWords * sizeof(unsigned long long)));
@@ -2359,10 +2393,11 @@ int32_t rt_scene_create_ex(const rt_scene_desc* desc, const int32_t* devices, in
     if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
     *out = nullptr;
     if (!desc) return fail(RT_ERR_NO_SCENE, "No scene loaded. Can't render.");
-    if (flags & ~RT_SCENE_DYNAMIC) return fail(RT_ERR_INVALID_ARG, "unknown scene flags");
+    if (flags & ~(RT_SCENE_DYNAMIC | RT_SCENE_DEFORMABLE)) return fail(RT_ERR_INVALID_ARG, "unknown scene flags");
     try {
         auto* s = new rt_scene();
-        s->host.dynamic = (flags & RT_SCENE_DYNAMIC) != 0;
+        s->host.deformable = (flags & RT_SCENE_DEFORMABLE) != 0;
+        s->host.dynamic = (flags & RT_SCENE_DYNAMIC) != 0 || s->host.deformable;
         std::string err;
         int32_t rc = build_host_scene(desc, s->host, err);
         if (rc != RT_OK) { delete s; return fail(rc, err); }
@@ -2403,6 +2438,10 @@ int32_t rt_scene_create_ex(const rt_scene_desc* desc, const int32_t* devices, in
         s->host.wnodes.clear(); s->host.wnodes.shrink_to_fit();
         s->host.lbox.clear(); s->host.lbox.shrink_to_fit();
         s->host.dyn.pbox.clear(); s->host.dyn.pbox.shrink_to_fit();
+        for (std::vector<int32_t>* v : {&s->host.def.vid, &s->host.def.rec_list, &s->host.def.wide_list,
+                                        &s->host.def.csr_off, &s->host.def.csr_tri}) {
+            v->clear(); v->shrink_to_fit();
+        }
         *out = s;
         return RT_OK;
     } catch (const std::bad_alloc&) {
@@ -2587,6 +2626,93 @@ static void refit_tree(const HostScene& S, DeviceReplica& r, const RefitLevels& 
                        S.wide_copy);
 }
 
+// ---- deforming meshes (rtcore.h; deform.h) ------------------------------------------------------------
+// The BLAS an RT_OBJ_MESH object produced, through the retained object -> BLAS map (a mesh whose id
+// a MeshInstance took over has no instance of its own, but its BLAS is still used); -1: none
+static int32_t deform_blas_of(const rt_scene* s, int32_t object_index) {
+    const HostScene& S = s->host;
+    if (object_index < 0 || object_index >= (int32_t)S.object_blas.size()) return -1;
+    const int32_t b = S.object_blas[(size_t)object_index];
+    if (b < 0 || (size_t)b >= S.def.blas.size() || S.def.blas[(size_t)b].verts <= 0) return -1;
+    return b;
+}
+
+int32_t rt_scene_mesh_vertex_count(const rt_scene* s, int32_t object_index, int64_t* num_positions) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!num_positions) return fail(RT_ERR_INVALID_ARG, "num_positions is NULL");
+    if (!s->host.deformable)
+        return fail(RT_ERR_UNSUPPORTED, "not a deformable scene (rt_scene_create_ex, RT_SCENE_DEFORMABLE)");
+    const int32_t b = deform_blas_of(s, object_index);
+    if (b < 0) return fail(RT_ERR_INVALID_ARG, "object is not a mesh with triangles");
+    *num_positions = s->host.def.blas[(size_t)b].verts;
+    return RT_OK;
+}
+
+int32_t rt_scene_set_mesh_positions(rt_scene* s, int32_t object_index, const double* positions, int64_t num_positions,
+                                    const double* normals, uint32_t flags) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!s->host.deformable)
+        return fail(RT_ERR_UNSUPPORTED, "not a deformable scene (rt_scene_create_ex, RT_SCENE_DEFORMABLE)");
+    if (flags & ~RT_POSITIONS_DEVICE) return fail(RT_ERR_INVALID_ARG, "unknown flags");
+    const int32_t b = deform_blas_of(s, object_index);
+    if (b < 0) return fail(RT_ERR_INVALID_ARG, "object is not a mesh with triangles");
+    const DeformBlas& f = s->host.def.blas[(size_t)b];
+    if (!positions || num_positions != f.verts)
+        return fail(RT_ERR_INVALID_ARG, "num_positions must equal the mesh's vertex count");
+    if (normals && f.normals != kNormalsSupplied)
+        return fail(RT_ERR_INVALID_ARG, "the mesh derives its normals from its positions: normals must be NULL");
+    try {
+        rt_scene::StagedDeform sd;
+        sd.blas = b;
+        sd.has_nrm = normals != nullptr;
+        if (flags & RT_POSITIONS_DEVICE) {
+            for (const double* p : {positions, normals}) {
+                if (!p) continue;
+                hipPointerAttribute_t at{};
+                if (hipPointerGetAttributes(&at, p) != hipSuccess) {
+                    (void)hipGetLastError();
+                    return fail(RT_ERR_UNSUPPORTED, "RT_POSITIONS_DEVICE: not a device pointer");
+                }
+                if (at.type != hipMemoryTypeDevice) return fail(RT_ERR_UNSUPPORTED, "RT_POSITIONS_DEVICE: not a device pointer");
+                for (const DeviceReplica& r : s->devs)
+                    if (r.device != at.device)
+                        return fail(RT_ERR_UNSUPPORTED, "RT_POSITIONS_DEVICE: every replica must be on the device that owns the buffer");
+            }
+            sd.dpos = positions;
+            sd.dnrm = normals;
+        } else {
+            sd.pos.assign(positions, positions + 3 * num_positions);
+            if (normals) sd.nrm.assign(normals, normals + 3 * num_positions);
+        }
+        std::lock_guard<std::mutex> lock(s->mu);
+        for (auto& e : s->staged_deform)
+            if (e.blas == b) { e = std::move(sd); return RT_OK; }
+        s->staged_deform.push_back(std::move(sd));
+        return RT_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    }
+}
+
+int32_t rt_scene_last_deform_stats(const rt_scene* s, rt_deform_stats* out) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
+    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
+    *out = s->last_deform;
+    return RT_OK;
+}
+
+// Commit scratch is touched by no render: it is replaced outright when it has to grow.
+static bool grow_plain(double** p, int64_t& cap, int64_t need) {
+    if (need <= cap && *p) return true;
+    (void)hipFree(*p);
+    *p = nullptr; cap = 0;
+    need = std::max<int64_t>(need, 1);
+    if (hipMalloc((void**)p, (size_t)need * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
+    cap = need;
+    return true;
+}
+
 int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
     if (stats) *stats = rt_commit_stats{};
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
@@ -2597,21 +2723,123 @@ int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
     auto ms_since = [](std::chrono::steady_clock::time_point t) {
         return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
     };
-    if (s->staged.empty()) {
+    s->last_deform = rt_deform_stats{};
+    if (s->staged.empty() && s->staged_deform.empty()) {
         if (stats) stats->total_ms = ms_since(t0);
         return RT_OK;
     }
     try {
         HostScene& S = s->host;
-        const DynScene& Y = S.dyn;
+        DynScene& Y = S.dyn;
+        const DeformScene& F = S.def;
         std::vector<std::pair<int32_t, std::array<double, 16>>> staged;
         staged.swap(s->staged);                              // a failed commit stages nothing
-        const size_t n = staged.size();
+        std::vector<rt_scene::StagedDeform> sdef;
+        sdef.swap(s->staged_deform);
+        const size_t n = staged.size(), nd = sdef.size();
+        const bool has_wide = !S.winst.empty();
+        rt_deform_stats dst{};
+        // the matrix instance k has once this commit is through
+        auto matrix_of = [&](int32_t k) -> const double* {
+            for (const auto& e : staged)
+                if (e.first == k) return e.second.data();
+            return S.insts[(size_t)k].l2w;
+        };
+        std::vector<char> deformed(Y.blas.size(), 0);
+        for (const auto& sd : sdef) deformed[(size_t)sd.blas] = 1;
+        int32_t rc = RT_OK;
+
+        // 0. staged positions: on the device, then checked there before anything changes (deform.h
+        //    k_deform_validate).  Host arrays go to one staging buffer per replica.
+        std::vector<int64_t> pos_off(nd, 0), nrm_off(nd, 0), part_off(nd, 0);
+        int64_t stage_total = 0, part_total = 2 * dev::kValidateParts, face_need = 0, vnorm_need = 0;
+        {
+            int64_t blocks = 0;
+            for (size_t m = 0; m < nd; ++m) {
+                const rt_scene::StagedDeform& sd = sdef[m];
+                const DeformBlas& f = F.blas[(size_t)sd.blas];
+                const DynBlas& y = Y.blas[(size_t)sd.blas];
+                pos_off[m] = stage_total; stage_total += (int64_t)sd.pos.size();
+                nrm_off[m] = stage_total; stage_total += (int64_t)sd.nrm.size();
+                part_off[m] = blocks;
+                blocks += (y.tri_end - y.tri_first + dev::kDeformBlock - 1) / dev::kDeformBlock;
+                if (f.normals == kNormalsSmooth) {
+                    face_need = std::max(face_need, 3 * (y.tri_end - y.tri_first));
+                    vnorm_need = std::max(vnorm_need, 3 * f.verts);
+                }
+                dst.triangles += y.tri_end - y.tri_first;
+            }
+            part_total = std::max(part_total, blocks);
+        }
+        auto stage_replica = [&](DeviceReplica& r) -> int32_t {
+            HIP_TRY(hipSetDevice(r.device));
+            if (!grow_plain(&r.def_stage, r.def_stage_cap, stage_total) || !grow_plain(&r.def_part, r.def_part_cap, part_total) ||
+                !grow_plain(&r.def_out, r.def_out_cap, 8 * (int64_t)nd) || !grow_plain(&r.def_face, r.def_face_cap, face_need) ||
+                !grow_plain(&r.def_vnorm, r.def_vnorm_cap, vnorm_need))
+                return fail(RT_ERR_OOM, "device allocation failed (deformation scratch)");
+            for (size_t m = 0; m < nd; ++m) {
+                const rt_scene::StagedDeform& sd = sdef[m];
+                if (!sd.pos.empty())
+                    HIP_TRY(hipMemcpy(r.def_stage + pos_off[m], sd.pos.data(), sd.pos.size() * sizeof(double), hipMemcpyHostToDevice));
+                if (!sd.nrm.empty())
+                    HIP_TRY(hipMemcpy(r.def_stage + nrm_off[m], sd.nrm.data(), sd.nrm.size() * sizeof(double), hipMemcpyHostToDevice));
+            }
+            return RT_OK;
+        };
+        auto pos_ptr = [&](const DeviceReplica& r, size_t m) -> const double* {
+            return sdef[m].dpos ? sdef[m].dpos : r.def_stage + pos_off[m];
+        };
+        auto nrm_ptr = [&](const DeviceReplica& r, size_t m) -> const double* {
+            if (!sdef[m].has_nrm) return nullptr;
+            return sdef[m].dnrm ? sdef[m].dnrm : r.def_stage + nrm_off[m];
+        };
+        if (nd > 0) {
+            DeviceReplica& r = s->devs[0];
+            if ((rc = stage_replica(r)) != RT_OK) return rc;
+            for (size_t m = 0; m < nd; ++m) {
+                const int64_t n3 = 3 * F.blas[(size_t)sdef[m].blas].verts;
+                const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(dev::kValidateParts, (n3 + dev::kDeformBlock - 1) / dev::kDeformBlock));
+                hipLaunchKernelGGL(dev::k_deform_validate, dim3((unsigned)parts), dim3(dev::kDeformBlock), 0, r.stream,
+                                   pos_ptr(r, m), n3, r.def_part);
+                hipLaunchKernelGGL(dev::k_deform_validate_final, dim3(1), dim3(64), 0, r.stream, r.def_part, parts,
+                                   r.def_out + 2 * m);
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipStreamSynchronize(r.stream));
+            std::vector<double> v(2 * nd, 0.0);
+            HIP_TRY(hipMemcpy(v.data(), r.def_out, v.size() * sizeof(double), hipMemcpyDeviceToHost));
+            for (size_t m = 0; m < nd; ++m) {
+                if (!(v[2 * m] == 1.0)) return fail(RT_ERR_INVALID_ARG, "staged positions are not all finite");
+                const DynBlas& y = Y.blas[(size_t)sdef[m].blas];
+                const double c = v[2 * m + 1] + std::fmax(std::fabs(y.motion[0]), std::fmax(std::fabs(y.motion[1]), std::fabs(y.motion[2])));
+                for (size_t i = 0; i < Y.inst_blas.size(); ++i) {
+                    if (Y.inst_blas[i] != sdef[m].blas) continue;
+                    const double* mt = matrix_of((int32_t)i);
+                    double reach = 0.0;
+                    for (int a = 0; a < 16; ++a) reach = std::max(reach, std::fabs(mt[a]));
+                    if (!(reach * (3.0 * c + 1.0) < 1e30))
+                        return fail(RT_ERR_INVALID_ARG, "staged positions put an instance of the mesh out of range");
+                }
+            }
+            dst.validate_ms = ms_since(t0);
+        }
         // 1. Instance.worldBounds of the moved instances: triangle meshes on the device (the union
-        //    over every triangle), spheres and planes (one primitive) here
+        //    over every triangle), spheres and planes (one primitive) here.  Instances of a deformed
+        //    mesh wait for its new triangle boxes (step 2c); their range is settled by step 0.
+        const auto tb0 = std::chrono::steady_clock::now();
         std::vector<double> nb(6 * n, 0.0), devb;
         std::vector<dev::RefitMove> moves;
         std::vector<size_t> move_of;
+        std::vector<char> later(n, 0);
+        auto move_for = [&](int32_t k, const double* m16) {
+            const DynBlas& y = Y.blas[(size_t)Y.inst_blas[(size_t)k]];
+            dev::RefitMove mv{};
+            std::memcpy(mv.m, m16, sizeof(mv.m));
+            for (int a = 0; a < 3; ++a) mv.motion[a] = y.motion[a];
+            mv.tri_first = (int32_t)y.tri_first; mv.tri_end = (int32_t)y.tri_end;
+            mv.blur = !(y.motion[0] == 0 && y.motion[1] == 0 && y.motion[2] == 0) ? 1 : 0;
+            return mv;
+        };
         for (size_t q = 0; q < n; ++q) {
             const int32_t k = staged[q].first;
             const DynBlas& y = Y.blas[(size_t)Y.inst_blas[(size_t)k]];
@@ -2619,20 +2847,17 @@ int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
                 special_instance_bounds(S, k, staged[q].second.data(), &nb[6 * q], &nb[6 * q + 3]);
                 continue;
             }
-            dev::RefitMove mv{};
-            std::memcpy(mv.m, staged[q].second.data(), sizeof(mv.m));
-            for (int a = 0; a < 3; ++a) mv.motion[a] = y.motion[a];
-            mv.tri_first = (int32_t)y.tri_first; mv.tri_end = (int32_t)y.tri_end;
-            mv.blur = !(y.motion[0] == 0 && y.motion[1] == 0 && y.motion[2] == 0) ? 1 : 0;
-            moves.push_back(mv);
+            if (deformed[(size_t)Y.inst_blas[(size_t)k]]) { later[q] = 1; continue; }
+            moves.push_back(move_for(k, staged[q].second.data()));
             move_of.push_back(q);
         }
-        int32_t rc = device_instance_bounds(s, moves, devb);
+        rc = device_instance_bounds(s, moves, devb);
         if (rc != RT_OK) return rc;
         for (size_t j = 0; j < move_of.size(); ++j) std::memcpy(&nb[6 * move_of[j]], &devb[6 * j], 6 * sizeof(double));
-        const double bounds_ms = ms_since(t0);
+        double bounds_ms = ms_since(tb0);
         // 2. nothing is changed unless every moved instance stays in range (float boxes stay finite)
         for (size_t q = 0; q < n; ++q) {
+            if (later[q]) continue;
             bool ok = true;
             for (int a = 0; a < 6; ++a) ok = ok && std::isfinite(nb[6 * q + a]) && std::fabs(nb[6 * q + a]) < 1e30;
             if (!S.winst.empty()) {
@@ -2643,12 +2868,133 @@ int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
             }
             if (!ok) return fail(RT_ERR_INVALID_ARG, "a staged transform puts its instance out of range");
         }
+        // 2a-c. the deformations (deform.h), the same kernels on every replica's stream: triangles,
+        //    triangle boxes, normals and leaf boxes; then the BLAS records and four-wide nodes level by
+        //    level; replica 0's root boxes and |e1||e2| come back to the host, and the instances of the
+        //    deformed meshes take new world bounds from the new triangle boxes
+        std::vector<std::pair<int32_t, std::array<double, 6>>> rebound;
+        if (nd > 0) {
+            const auto td0 = std::chrono::steady_clock::now();
+            auto run_of = [&](const DeviceReplica& r, const DynBlas& y) {
+                dev::DeformRun R{};
+                R.tris = r.tris; R.pbox = r.pbox; R.tri_end = (int32_t)y.tri_end;
+                R.blur = !(y.motion[0] == 0 && y.motion[1] == 0 && y.motion[2] == 0) ? 1 : 0;
+                for (int a = 0; a < 3; ++a) R.motion[a] = y.motion[a];
+                return R;
+            };
+            auto grid = [](int64_t items) { return dim3((unsigned)std::max<int64_t>(1, (items + dev::kDeformBlock - 1) / dev::kDeformBlock)); };
+            for (DeviceReplica& r : s->devs) {
+                if (&r != &s->devs[0] && (rc = stage_replica(r)) != RT_OK) return rc;
+                HIP_TRY(hipSetDevice(r.device));
+                if (!r.pbox || !r.vid) return fail(RT_ERR_DEVICE, "deformable scene without triangle boxes");
+                for (size_t m = 0; m < nd; ++m) {
+                    const DeformBlas& f = F.blas[(size_t)sdef[m].blas];
+                    const DynBlas& y = Y.blas[(size_t)sdef[m].blas];
+                    const int64_t nt = y.tri_end - y.tri_first;
+                    dev::DeformMesh M{};
+                    M.pos = pos_ptr(r, m); M.vid = r.vid;
+                    const double* new_nrm = nrm_ptr(r, m);       // newly supplied per-vertex normals, or null
+                    M.tri_first = (int32_t)y.tri_first; M.tri_end = (int32_t)y.tri_end;
+                    M.prim_base = f.prim_base; M.normals = f.normals;
+                    const dev::DeformRun R = run_of(r, y);
+                    hipLaunchKernelGGL(dev::k_deform_tris, grid(nt), dim3(dev::kDeformBlock), 0, r.stream, M, r.tris, r.pbox,
+                                       r.normals, r.def_face, r.def_part + part_off[m]);
+                    if (f.normals == kNormalsSmooth) {
+                        hipLaunchKernelGGL(dev::k_vertex_normals, grid(f.verts), dim3(dev::kDeformBlock), 0, r.stream,
+                                           r.csr_off + f.csr_off_first, r.csr_tri + f.csr_first, f.verts, r.def_face, r.def_vnorm);
+                        hipLaunchKernelGGL(dev::k_gather_normals, grid(nt), dim3(dev::kDeformBlock), 0, r.stream, r.vid,
+                                           M.tri_first, M.tri_end, (const double*)r.def_vnorm, r.normals);
+                    } else if (f.normals == kNormalsSupplied && new_nrm) {
+                        hipLaunchKernelGGL(dev::k_gather_normals, grid(nt), dim3(dev::kDeformBlock), 0, r.stream, r.vid,
+                                           M.tri_first, M.tri_end, new_nrm, r.normals);
+                    }
+                    if (has_wide)
+                        hipLaunchKernelGGL(dev::k_leaf_boxes, grid(nt), dim3(dev::kDeformBlock), 0, r.stream, R, M.tri_first, r.lbox);
+                }
+                HIP_TRY(hipGetLastError());
+            }
+            for (DeviceReplica& r : s->devs) {
+                HIP_TRY(hipSetDevice(r.device));
+                HIP_TRY(hipStreamSynchronize(r.stream));
+            }
+            dst.deform_ms = ms_since(td0);
+            const auto tr0 = std::chrono::steady_clock::now();
+            for (DeviceReplica& r : s->devs) {
+                HIP_TRY(hipSetDevice(r.device));
+                for (size_t m = 0; m < nd; ++m) {
+                    const DeformBlas& f = F.blas[(size_t)sdef[m].blas];
+                    const DynBlas& y = Y.blas[(size_t)sdef[m].blas];
+                    const int64_t nt = y.tri_end - y.tri_first;
+                    const dev::DeformRun R = run_of(r, y);
+                    for (size_t l = 0; l + 1 < f.rec_off.size(); ++l) {
+                        const int32_t cnt = (int32_t)(f.rec_off[l + 1] - f.rec_off[l]);
+                        if (cnt <= 0) continue;
+                        hipLaunchKernelGGL(dev::k_refit_recs, grid(2 * (int64_t)cnt), dim3(dev::kDeformBlock), 0, r.stream, r.recs,
+                                           (const int32_t*)(r.rec_list + f.rec_off[l]), cnt, R);
+                    }
+                    hipLaunchKernelGGL(dev::k_blas_root, dim3(1), dim3(64), 0, r.stream, (const WRec*)r.recs, f.root_ref, R,
+                                       (const double*)(r.def_part + part_off[m]),
+                                       (int)((nt + dev::kDeformBlock - 1) / dev::kDeformBlock), r.def_out + 8 * m);
+                    if (has_wide && r.wnodes && f.wroot >= 0 && f.wide_off.size() > 1) {
+                        for (size_t l = 0; l + 1 < f.wide_off.size(); ++l) {
+                            const int32_t cnt = (int32_t)(f.wide_off[l + 1] - f.wide_off[l]);
+                            if (cnt <= 0) continue;
+                            hipLaunchKernelGGL(dev::k_refit_blas_level, grid(4 * (int64_t)cnt), dim3(dev::kDeformBlock), 0, r.stream,
+                                               r.wnodes, (const int32_t*)(r.wide_list + f.wide_off[l]), cnt, (const double*)r.lbox);
+                        }
+                        const int64_t nn = f.wide_off.back() - f.wide_off.front();
+                        hipLaunchKernelGGL(dev::k_octant_copies, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, r.stream, r.wnodes,
+                                           (const int32_t*)(r.wide_list + f.wide_off.front()), nn, S.wide_copy);
+                    }
+                }
+                HIP_TRY(hipGetLastError());
+            }
+            for (DeviceReplica& r : s->devs) {
+                HIP_TRY(hipSetDevice(r.device));
+                HIP_TRY(hipStreamSynchronize(r.stream));
+            }
+            std::vector<double> roots(8 * nd, 0.0);
+            HIP_TRY(hipSetDevice(s->devs[0].device));
+            HIP_TRY(hipMemcpy(roots.data(), s->devs[0].def_out, roots.size() * sizeof(double), hipMemcpyDeviceToHost));
+            dst.blas_refit_ms = ms_since(tr0);
+            // the host's copies: the pruning margin's constant, the BLAS root box of every instance of
+            // the mesh and the widening bound of its local rays (scene.cpp build_wide_tw: bcoord)
+            const auto tb1 = std::chrono::steady_clock::now();
+            std::vector<dev::RefitMove> dmoves;
+            std::vector<int32_t> dinst;
+            for (size_t m = 0; m < nd; ++m) {
+                const double* o = &roots[8 * m];
+                Y.blas[(size_t)sdef[m].blas].P = o[6];
+                double bc = 0.0;
+                for (int a = 0; a < 6; ++a) bc = std::fmax(bc, std::fabs(o[a]));
+                for (size_t i = 0; i < Y.inst_blas.size(); ++i) {
+                    if (Y.inst_blas[i] != sdef[m].blas) continue;
+                    DInstance& di = S.insts[i];
+                    for (int a = 0; a < 3; ++a) { di.root_lo[a] = o[a]; di.root_hi[a] = o[3 + a]; }
+                    if (has_wide) S.winst[i].bcoord = bc;
+                    dmoves.push_back(move_for((int32_t)i, matrix_of((int32_t)i)));
+                    dinst.push_back((int32_t)i);
+                }
+            }
+            std::vector<double> db;
+            rc = device_instance_bounds(s, dmoves, db);
+            if (rc != RT_OK) return rc;
+            for (size_t j = 0; j < dinst.size(); ++j) {
+                std::array<double, 6> b6;
+                std::memcpy(b6.data(), &db[6 * j], sizeof(b6));
+                rebound.push_back({dinst[j], b6});
+            }
+            bounds_ms += ms_since(tb1);
+            dst.meshes_deformed = (int64_t)nd;
+            dst.instances_rebounded = (int64_t)dinst.size();
+        }
         // 3. host: DInstance, TLAS bounds bottom-up, TLAS records, tbox, the margins' constants
         const auto t1 = std::chrono::steady_clock::now();
         for (size_t q = 0; q < n; ++q) {
             set_instance_matrix(S, staged[q].first, staged[q].second.data());
-            std::memcpy(&S.inst_bounds[6 * (size_t)staged[q].first], &nb[6 * q], 6 * sizeof(double));
+            if (!later[q]) std::memcpy(&S.inst_bounds[6 * (size_t)staged[q].first], &nb[6 * q], 6 * sizeof(double));
         }
+        for (const auto& e : rebound) std::memcpy(&S.inst_bounds[6 * (size_t)e.first], e.second.data(), 6 * sizeof(double));
         std::string err;
         rc = refit_host_scene(S, err);
         if (rc != RT_OK) return fail(rc, err);
@@ -2671,6 +3017,7 @@ int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
             HIP_TRY(hipStreamSynchronize(r.stream));
         }
         drop_tile_orders(s);
+        s->last_deform = dst;
         if (stats) {
             stats->instances_moved = (int64_t)n;
             stats->bounds_ms = bounds_ms;
@@ -3536,10 +3883,11 @@ static int32_t wide_dump_fill(const HostScene& S, const WideArrays& A, rt_wide_d
 int32_t rt_debug_wide_build(const rt_scene_desc* desc, uint32_t flags, rt_wide_dump* io) {
     if (!desc) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
     if (!io) return fail(RT_ERR_INVALID_ARG, "NULL argument");
-    if (flags & ~RT_SCENE_DYNAMIC) return fail(RT_ERR_INVALID_ARG, "unknown scene flags");
+    if (flags & ~(RT_SCENE_DYNAMIC | RT_SCENE_DEFORMABLE)) return fail(RT_ERR_INVALID_ARG, "unknown scene flags");
     try {
         HostScene S;
-        S.dynamic = (flags & RT_SCENE_DYNAMIC) != 0;
+        S.deformable = (flags & RT_SCENE_DEFORMABLE) != 0;
+        S.dynamic = (flags & RT_SCENE_DYNAMIC) != 0 || S.deformable;
         S.keep_tri_src = true;
         std::string err;
         const int32_t rc = build_host_scene(desc, S, err);

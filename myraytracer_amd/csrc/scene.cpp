@@ -1072,6 +1072,11 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
     };
 
     std::vector<int> meshInstanceObj;
+    // deformable scenes: per `triangles[]` entry its three mesh-local vertex ids, and per BLAS what
+    // a deformation needs (scene.h DeformBlas); the index arrays are gone after this function
+    std::vector<int32_t> triVid;
+    std::vector<DeformBlas> defBlas;
+    S.object_blas.assign((size_t)std::max(0, d->num_objects), -1);
     for (int oi = 0; oi < d->num_objects; ++oi) {
         const rt_object& o = d->objects[oi];
         if (o.kind == RT_OBJ_SPHERE || o.kind == RT_OBJ_PLANE) {            // RTContext.swift:122-192
@@ -1211,12 +1216,34 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
             bb.triIndex[t] = start + t;
         }
         });
+        if (S.deformable && triCount > 0) {
+            triVid.resize(3 * (size_t)(start + triCount), 0);
+            for (int64_t t = 0; t < 3 * triCount; ++t) triVid[3 * (size_t)start + (size_t)t] = (int32_t)(I[t] - off);
+            DeformBlas db;
+            db.verts = nPos;
+            db.normals = Nn ? kNormalsSupplied : (isSmooth ? kNormalsSmooth : kNormalsFlat);
+            db.prim_base = (int32_t)start;
+            if (db.normals == kNormalsSmooth) {          // vertex -> incident corners, ascending triangle order
+                db.csr_off_first = (int64_t)S.def.csr_off.size();
+                db.csr_first = (int64_t)S.def.csr_tri.size();
+                std::vector<int32_t> cnt((size_t)nPos + 1, 0);
+                for (int64_t t = 0; t < 3 * triCount; ++t) cnt[(size_t)(I[t] - off) + 1]++;
+                for (int64_t v = 0; v < nPos; ++v) cnt[(size_t)v + 1] += cnt[(size_t)v];
+                S.def.csr_off.insert(S.def.csr_off.end(), cnt.begin(), cnt.end());
+                S.def.csr_tri.resize((size_t)db.csr_first + 3 * (size_t)triCount);
+                for (int64_t t = 0; t < 3 * triCount; ++t)
+                    S.def.csr_tri[(size_t)db.csr_first + (size_t)cnt[(size_t)(I[t] - off)]++] = (int32_t)(t / 3);
+            }
+            defBlas.resize(blases.size() + 1);
+            defBlas.back() = std::move(db);
+        }
         if (std::find(meshOrder.begin(), meshOrder.end(), o.id) == meshOrder.end()) meshOrder.push_back(o.id);
         if (triCount > 0) {
             blases.push_back(std::move(bb));
             Base base{};
             base.blas = (int)blases.size() - 1; base.material = o.material_id;
             base.obj = oi;
+            S.object_blas[(size_t)oi] = base.blas;
             std::memcpy(base.M, o.transform, sizeof(base.M));
             instanceByID[o.id] = base;
         } else {
@@ -1284,6 +1311,9 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
                 r.last = (q == count - 1) ? 1 : 0;
                 r.prim = (int32_t)g;
                 S.tris.push_back(r);
+                if (S.deformable)
+                    for (size_t k = 0; k < 3; ++k)
+                        S.def.vid.push_back(3 * (size_t)g + k < triVid.size() ? triVid[3 * (size_t)g + k] : 0);
                 const D3 ns[3] = {t.n0, t.n1, t.n2};
                 for (int k = 0; k < 3; ++k) { S.normals.push_back(ns[k].x); S.normals.push_back(ns[k].y); S.normals.push_back(ns[k].z); }
             }
@@ -1300,7 +1330,8 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         bb.prims = PrimSet();
     }
     S.blas_records = (int64_t)S.recs.size();
-    if (!S.has_special && !S.tris.empty()) {   // compact triangles when every vertex is a float
+    // (a deformable scene keeps the FP64 layouts: a deformation does not keep vertices floats)
+    if (!S.has_special && !S.tris.empty() && !S.deformable) {   // compact triangles when every vertex is a float
         bool exact = true;
         auto fx = [](double x) { return (double)(float)x == x; };
         for (size_t q = 0; q < S.tris.size() && exact; ++q) {
@@ -1324,7 +1355,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         }
     }
     {   // compact BLAS records when every bound survives a float32 round trip exactly
-        bool exact = true;
+        bool exact = !S.deformable;
         for (int64_t q = 0; q < S.blas_records && exact; ++q)
             for (int c = 0; c < 2; ++c)
                 for (int k = 0; k < 3; ++k) {
@@ -1567,6 +1598,40 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         };
         levels(S.winst.empty() ? -1 : S.wide_root, Y.tlas_levels);
         levels(S.fit_root, Y.fit_levels);
+        if (S.deformable) {
+            DeformScene& F = S.def;
+            defBlas.resize(blases.size());
+            F.blas = std::move(defBlas);
+            for (size_t b = 0; b < blases.size(); ++b) {
+                DeformBlas& f = F.blas[b];
+                f.root_ref = blases[b].root_ref;
+                if (f.verts == 0) continue;
+                // the BLAS's records by depth, deepest first: a record's children come before it
+                std::vector<std::vector<int32_t>> lv;
+                if (f.root_ref >= 0) lv.push_back({f.root_ref});
+                while (!lv.empty()) {
+                    std::vector<int32_t> next;
+                    for (int32_t n : lv.back())
+                        for (int c = 0; c < 2; ++c)
+                            if (S.recs[(size_t)n].ref[c] >= 0) next.push_back(S.recs[(size_t)n].ref[c]);
+                    if (next.empty()) break;
+                    lv.push_back(std::move(next));
+                }
+                for (size_t l = lv.size(); l-- > 0;) {
+                    f.rec_off.push_back((int64_t)F.rec_list.size());
+                    F.rec_list.insert(F.rec_list.end(), lv[l].begin(), lv[l].end());
+                }
+                f.rec_off.push_back((int64_t)F.rec_list.size());
+                // its part of the four-wide array (shared by the instances of the mesh)
+                f.wroot = -1;
+                for (size_t i = 0; i < insts.size() && !S.winst.empty(); ++i)
+                    if ((size_t)insts[i].blas == b) { f.wroot = S.winst[i].wroot; break; }
+                RefitLevels W;
+                levels(f.wroot, W);
+                for (int64_t o : W.off) f.wide_off.push_back((int64_t)F.wide_list.size() + o);
+                F.wide_list.insert(F.wide_list.end(), W.nodes.begin(), W.nodes.end());
+            }
+        }
     }
     if (trace && S.fit_root >= 0)
         std::fprintf(stderr, "[build] fit: %zu pairs, %lld nodes, depth %lld, coord %.6g, %.1f ms\n", S.fpairs.size(),

@@ -67,6 +67,31 @@ struct DynScene {
     bool fit_blocked = false;              // an instance exceeds kFitKappa: tw_walk until a commit passes
 };
 
+// ---- deformable scenes (rt_scene_create_ex with RT_SCENE_DEFORMABLE; deform.h) ---------------------
+// What rt_scene_set_mesh_positions / rt_scene_commit need to bring a BLAS up to date with new
+// vertex positions on the device, the topology kept (BVHBuilder.refit, BVH.swift:254-291): per
+// TriRec its three mesh-local vertex ids; per BLAS its vertex count, how its normals were made, its
+// WRec records and its four-wide nodes by level (deepest first) and, for derived smooth normals,
+// the vertex -> incident triangle adjacency (CSR; a vertex's entries in ascending triangle order,
+// one per corner, so that a vertex's sum runs in the builder's order, scene.cpp "normals").
+constexpr int32_t kNormalsFlat = 0, kNormalsSupplied = 1, kNormalsSmooth = 2;
+struct DeformBlas {
+    int64_t verts = 0;                     // 0: not a mesh (a triangle object, a sphere, a plane)
+    int32_t normals = kNormalsFlat;
+    int32_t prim_base = 0;                 // TriRec::prim - prim_base = the mesh's own triangle index
+    int32_t root_ref = 0;                  // BLAS root (layout.h ref encoding)
+    int32_t wroot = -1;                    // its four-wide root (DWideInst::wroot); < 0: no node
+    std::vector<int64_t> rec_off;          // level l: DeformScene::rec_list[rec_off[l], rec_off[l + 1])
+    std::vector<int64_t> wide_off;         // ... wide_list
+    int64_t csr_off_first = 0;             // kNormalsSmooth: csr_off[csr_off_first + v], verts + 1 entries,
+    int64_t csr_first = 0;                 //   counting from csr_tri[csr_first]
+};
+struct DeformScene {
+    std::vector<DeformBlas> blas;
+    std::vector<int32_t> vid;              // 3 per TriRec, leaf order (dropped after upload)
+    std::vector<int32_t> rec_list, wide_list, csr_off, csr_tri;   // (dropped after upload)
+};
+
 struct HostScene {
     // ---- scene-level parameters
     double eps = 0, shadow_eps = 0;
@@ -97,6 +122,9 @@ struct HostScene {
     bool identity = false;                 // all instances identity & static (unified walk)
     bool dynamic = false;                  // set before build_host_scene: identity stays false, dyn is filled
     DynScene dyn;
+    bool deformable = false;               // set before build_host_scene (implies dynamic): FP64 layouts only
+    DeformScene def;
+    std::vector<int32_t> object_blas;      // per scene object: the BLAS an RT_OBJ_MESH produced, or -1
     std::vector<double> inst_bounds;       // 6 per instance: Instance.worldBounds (lo, hi)
     std::vector<int32_t> object_inst;      // per scene object: the instance it produced, or -1
     int64_t blas_records = 0, tlas_records = 0;

@@ -113,22 +113,26 @@ class RenderProgress:                    # Models/RenderProgress.swift:8-14
 class RayTracerEngine:
     """Device-resident scene + renderer (one full replica per listed GPU)."""
 
-    def __init__(self, scene: Scene, devices: Optional[Sequence[int]] = None, dynamic: bool = False):
+    def __init__(self, scene: Scene, devices: Optional[Sequence[int]] = None, dynamic: bool = False,
+                 deformable: bool = False):
         """dynamic: instances and cameras may move between renders (set_transform / set_camera /
-        commit; rt_scene_create_ex with RT_SCENE_DYNAMIC)."""
+        commit; rt_scene_create_ex with RT_SCENE_DYNAMIC).  deformable: mesh vertices may move as
+        well (set_positions; RT_SCENE_DEFORMABLE, which implies dynamic)."""
         lib = load_library()
         self.scene = scene
         self._packed = scene.to_desc()
         handle = C.c_void_p()
         devs = list(devices) if devices else [0]
         arr = (C.c_int32 * len(devs))(*devs)
-        if dynamic:
-            _check(lib.rt_scene_create_ex(self._packed.ptr, arr, len(devs), A.RT_SCENE_DYNAMIC, C.byref(handle)))
+        flags = (A.RT_SCENE_DYNAMIC if dynamic else 0) | (A.RT_SCENE_DEFORMABLE if deformable else 0)
+        if flags:
+            _check(lib.rt_scene_create_ex(self._packed.ptr, arr, len(devs), flags, C.byref(handle)))
         else:
             _check(lib.rt_scene_create(self._packed.ptr, arr, len(devs), C.byref(handle)))
         self._h = handle
         self.devices = devs
-        self.dynamic = bool(dynamic)
+        self.deformable = bool(deformable)
+        self.dynamic = bool(dynamic) or self.deformable
 
     @classmethod
     def from_file(cls, path, format: str = "auto", devices: Optional[Sequence[int]] = None) -> "RayTracerEngine":
@@ -210,6 +214,69 @@ class RayTracerEngine:
         """Apply the staged transforms (rt_scene_commit): blocks until every replica is updated."""
         st = A.rt_commit_stats()
         _check(load_library().rt_scene_commit(self._h, C.byref(st)))
+        return st
+
+    # -- deforming meshes (BVHBuilder.refit applied to a BLAS, BVH.swift:254-291)
+    def vertex_count(self, object_index: int) -> int:
+        """The vertex count of mesh object `object_index` (rt_scene_mesh_vertex_count)."""
+        n = C.c_int64(0)
+        _check(load_library().rt_scene_mesh_vertex_count(self._h, int(object_index), C.byref(n)))
+        return int(n.value)
+
+    def set_positions(self, object_index: int, positions, normals=None, mirror: bool = True):
+        """Stage new vertex positions (and, for a mesh created with per-vertex normals, optionally
+        new normals) for mesh object `object_index`; commit() applies them.  `positions` / `normals`
+        are (N, 3) float64 numpy arrays, or contiguous float64 torch tensors on the scene's device,
+        which are passed by pointer and must stay unchanged until commit() returns.  With `mirror`
+        self.scene.objects[object_index] follows (a PLY-backed mesh becomes an inline mesh), so
+        oracle.OracleScene(self.scene) stays the reference scene of the next committed state.
+        The mirror follows when the positions are staged, as set_transform's does: a commit() that
+        is refused (RT_ERR_INVALID_ARG) drops what was staged, and self.scene then describes a pose
+        the engine never took - stage a valid pose again, or pass mirror=False and keep the mirror
+        yourself, where a refusal is possible."""
+        def unpack(a):
+            if a is None:
+                return None, None, False
+            if hasattr(a, "data_ptr"):                       # a torch tensor
+                if str(a.dtype) != "torch.float64" or not a.is_contiguous() or a.dim() != 2 or a.shape[1] != 3:
+                    raise ValueError("a tensor must be a contiguous float64 (N, 3)")
+                if a.device.type == "cpu":
+                    return unpack(a.numpy())
+                return a, np.asarray(a.detach().cpu().numpy(), dtype=np.float64).reshape(-1, 3) if mirror else None, True
+            h = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+            if h.ndim != 2 or h.shape[1] != 3:
+                raise ValueError("positions / normals are (N, 3) arrays")
+            return h, h, False
+
+        p, p_host, p_dev = unpack(positions)
+        q, q_host, q_dev = unpack(normals)
+        if p is None:
+            raise ValueError("positions is None")
+        if q is not None and q_dev != p_dev:
+            raise ValueError("positions and normals must both be host arrays or both device tensors")
+        count = int(p.shape[0]) if p.ndim == 2 else int(p.numel() // 3)
+        if q is not None and (int(q.shape[0]) if q.ndim == 2 else int(q.numel() // 3)) != count:
+            raise ValueError("normals must have one row per position")
+        ptr = (lambda x: None if x is None else C.c_void_p(x.data_ptr() if p_dev else x.ctypes.data))
+        _check(load_library().rt_scene_set_mesh_positions(self._h, int(object_index), ptr(p), count, ptr(q),
+                                                          A.RT_POSITIONS_DEVICE if p_dev else 0))
+        if not mirror:
+            return
+        o = self.scene.objects[object_index]
+        if o.ply_path is not None:                           # the PLY's arrays, as the build read them
+            m = ply_load(o.ply_path)
+            o.indices = np.ascontiguousarray(m["indices"], dtype=np.int32).reshape(-1, 3)
+            o.indices_one_based = False
+            o.normals = m["normals"]
+            o.ply_path = None
+        o.positions = p_host.copy()
+        if q_host is not None:
+            o.normals = q_host.copy()
+
+    def last_deform_stats(self) -> A.rt_deform_stats:
+        """What the last commit() did for deformations (rt_scene_last_deform_stats)."""
+        st = A.rt_deform_stats()
+        _check(load_library().rt_scene_last_deform_stats(self._h, C.byref(st)))
         return st
 
     def instance_bounds(self, instance: int):
