@@ -193,6 +193,56 @@ public:
         check(rt_scene_last_deform_stats(scene_, &st));
         return st;
     }
+    /* Ray queries (rtcore.h "ray queries"): the scene's production walks on caller-given rays, host
+     * arrays (xyz triples; tlimit / time empty = none).  queryClosest fills the fields `want` names;
+     * `declared` null lets the device find the batch's bounds. */
+    struct RayHits {
+        std::vector<double> t, uv, point, normal;
+        std::vector<int32_t> ids;                           /* object, face, instance, material */
+        std::vector<uint8_t> flags;                         /* RT_HIT_* */
+    };
+    enum : uint32_t { WantT = 1, WantUV = 2, WantIds = 4, WantPoint = 8, WantNormal = 16, WantFlags = 32 };
+    RayHits queryClosest(const std::vector<double>& origins, const std::vector<double>& dirs,
+                         const std::vector<double>& tmin = {}, const std::vector<double>& time = {},
+                         uint32_t want = WantT | WantUV | WantIds, const rt_query_bounds* declared = nullptr,
+                         uint32_t flags = 0u, int32_t slot = 0) {
+        const int64_t n = (int64_t)origins.size() / 3;
+        if (dirs.size() != origins.size() || (!tmin.empty() && (int64_t)tmin.size() != n) ||
+            (!time.empty() && (int64_t)time.size() != n))
+            throw RenderError(RT_ERR_INVALID_ARG, "ray arrays differ in length");
+        RayHits h;
+        rt_hit_batch hb{};
+        if (want & WantT) { h.t.resize((size_t)n); hb.t = h.t.data(); }
+        if (want & WantUV) { h.uv.resize(2 * (size_t)n); hb.uv = h.uv.data(); }
+        if (want & WantIds) { h.ids.resize(4 * (size_t)n); hb.ids = h.ids.data(); }
+        if (want & WantPoint) { h.point.resize(3 * (size_t)n); hb.point = h.point.data(); }
+        if (want & WantNormal) { h.normal.resize(3 * (size_t)n); hb.normal = h.normal.data(); }
+        if (want & WantFlags) { h.flags.resize((size_t)n); hb.flags = h.flags.data(); }
+        const rt_ray_batch rb{origins.data(), dirs.data(), tmin.empty() ? nullptr : tmin.data(),
+                              time.empty() ? nullptr : time.data()};
+        check(rt_query_closest(scene_, slot, n, &rb, &hb, declared, flags & ~RT_QUERY_DEVICE, nullptr));
+        return h;
+    }
+    /* Per ray 0 = free, 1 = blocked, 2 = not traced (beyond `declared`, or non-finite). */
+    std::vector<uint8_t> queryOccluded(const std::vector<double>& origins, const std::vector<double>& dirs,
+                                       const std::vector<double>& tmax = {}, const std::vector<double>& time = {},
+                                       const rt_query_bounds* declared = nullptr, uint32_t flags = 0u,
+                                       int32_t slot = 0) {
+        const int64_t n = (int64_t)origins.size() / 3;
+        if (dirs.size() != origins.size() || (!tmax.empty() && (int64_t)tmax.size() != n) ||
+            (!time.empty() && (int64_t)time.size() != n))
+            throw RenderError(RT_ERR_INVALID_ARG, "ray arrays differ in length");
+        std::vector<uint8_t> out((size_t)n);
+        const rt_ray_batch rb{origins.data(), dirs.data(), tmax.empty() ? nullptr : tmax.data(),
+                              time.empty() ? nullptr : time.data()};
+        check(rt_query_occluded(scene_, slot, n, &rb, out.data(), declared, flags & ~RT_QUERY_DEVICE, nullptr));
+        return out;
+    }
+    rt_query_counts lastQueryStats(int32_t slot = 0) const {
+        rt_query_counts st{};
+        check(rt_query_stats(scene_, slot, &st));
+        return st;
+    }
     /* Instance.worldBounds of an instance (any scene), as of the last commit. */
     void instanceBounds(int32_t instance, double lo[3], double hi[3]) const {
         check(rt_scene_instance_bounds(scene_, instance, lo, hi));

@@ -55,7 +55,8 @@
  *      rt_scene_set_camera, rt_scene_instance_bounds, rt_scene_commit.
  *      Appended later without moving the version, as the rt_debug_wide_* pair was (callers detect
  *      them by symbol): deforming meshes - RT_SCENE_DEFORMABLE, rt_scene_mesh_vertex_count,
- *      rt_scene_set_mesh_positions, rt_scene_last_deform_stats. */
+ *      rt_scene_set_mesh_positions, rt_scene_last_deform_stats; ray queries - rt_query_closest,
+ *      rt_query_occluded, rt_query_stats. */
 #define RT_ABI_VERSION 5
 
 #ifdef __cplusplus
@@ -316,6 +317,7 @@ int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);
  *                        0 = the TLAS / per-BLAS four-wide walk (tw_walk)
  *   queue_tail (2)       compacted bounce render: levels >= this one traced depth-first in one
  *                        launch (render.hip k_bounce_tail); 0 = one launch per level
+ *   query_batch (4194304)  ray queries: rays per launch and per host staging pass (64 .. 2^30)
  * Unknown names and out-of-range values return RT_ERR_INVALID_ARG.  Set options between
  * renders (not while renders of the scene are in flight).  The test hooks below are refused
  * here (RT_ERR_INVALID_ARG); rt_scene_get_option reads every option. */
@@ -553,6 +555,93 @@ int32_t rt_debug_rcp(int32_t n, const double* x, double* out_fast, double* out_d
 int32_t rt_debug_wave_times(rt_scene* scene, int32_t slot, int32_t camera_index, int32_t chunk_first,
                             int32_t chunk_step, double* d_out_rgb, uint64_t* out, int64_t max_waves,
                             int64_t* n_waves);
+
+/* ---- ray queries ------------------------------------------------
+ * The scene's production walks on caller-given rays, from host or device arrays, with full hit
+ * records.  Added without moving RT_ABI_VERSION: detect the entry points by symbol, as the
+ * deformation entry points are.  A ray means what it means to rt_debug_trace_rays /
+ * rt_debug_occluded_rays: rt_query_closest = intersectTLAS (RTContext.swift:619-720) with tMin,
+ * rt_query_occluded = occludedTLAS (:724-781) with tMax, through the walk the scene's options
+ * select (wide, unified, unified_transformed, fit).
+ *
+ *   ids       4 per ray: [0] the scene object the geometry belongs to (a MeshInstance: the instance
+ *             object; rt_scene_instance_of_object gives the other direction; -1 for a mesh whose id
+ *             a MeshInstance took over), [1] the triangle's index in its own object's face list as
+ *             the scene was given (a PLY: the order rt_ply_load returns; RT_OBJ_TRIANGLE: 0; spheres
+ *             and planes: -1), [2] the flattened instance, [3] the instance's material.  All -1 on a
+ *             miss.  The first query that asks for ids uploads a face table to the replica (4 bytes
+ *             per triangle record plus 4 per instance, rt_scene_info.device_bytes from then on).
+ *   flags     RT_QUERY_DEVICE: every pointer of the batches (and `out`) is a device pointer on the
+ *             slot's device (else RT_ERR_UNSUPPORTED); the work is enqueued on `stream` (a
+ *             hipStream_t, NULL = default).  Without it the arrays are host arrays, staged through
+ *             the slot's query scratch, and the call returns with the results in them.
+ *   declared  NULL: one reduction kernel finds the batch's largest origin distance to the scene
+ *             centre, largest |origin coordinate| and largest |d|, which size the pruning margin and
+ *             the four-wide walk's widening exactly as the host loop of the debug entry points does;
+ *             the call synchronises `stream` once to read them.  Not NULL: the caller's bounds are
+ *             used instead and a device query only enqueues (no synchronisation, nothing read back).
+ *             A ray beyond any declared bound is NOT traced: its record is a miss with
+ *             RT_HIT_OUT_OF_BOUNDS (rt_query_occluded: out = 2).  A ray with a non-finite origin or
+ *             direction component is never traced either way: RT_HIT_NON_FINITE (out = 2), and it
+ *             does not enter the reduction.
+ *             Forming safe bounds: origin_coord and dir_norm are the batch's own largest |origin
+ *             coordinate| and |d|.  origin_reach is measured from the centre of the scene's world
+ *             box, which moves with rt_scene_commit; the centre lies inside the union of the boxes
+ *             rt_scene_instance_bounds returns, so the largest distance from an origin to the
+ *             farthest corner of that union is always enough.  rt_query_counts.bounds of a query
+ *             with declared == NULL reports the exact maxima of that batch at the current pose.
+ *             Any bound above the true maximum is safe (larger bounds only widen the margins).
+ *
+ * Large batches run as several launches (render option query_batch, rays per launch) under one
+ * set of constants.  Queries of ONE slot share its scratch and statistics: issue them on one stream
+ * (or order them externally).  A query holds the scene's lock only while it is prepared, not while
+ * it runs: ordering it against rt_scene_commit is the caller's job, as for rt_render_device.
+ * Scratch that grows is retired, not freed, under queries still queued.
+ * RT_ERR_INVALID_ARG: a bad slot, n < 0, NULL origin / dir with n > 0, unknown flags, a negative
+ * or non-finite member of `declared`; after a refusal nothing has been enqueued. */
+typedef struct rt_ray_batch {       /* n rays; arrays of doubles */
+    const double *origin, *dir;     /* 3 per ray */
+    const double *tlimit;           /* closest: tMin, NULL = 0; occluded: tMax, NULL = +inf */
+    const double *time;             /* NULL = 0 */
+} rt_ray_batch;
+typedef struct rt_hit_batch {       /* every pointer optional (NULL = not written) */
+    double  *t;                     /* +inf on a miss */
+    double  *uv;                    /* 2 per ray: Moeller-Trumbore u, v (0 for spheres / planes and misses) */
+    int32_t *ids;                   /* 4 per ray: object, face within that object, instance, material */
+    double  *point, *normal;        /* 3 per ray, as rt_debug_trace_rays returns them */
+    uint8_t *flags;                 /* RT_HIT_* bits */
+} rt_hit_batch;
+typedef struct rt_query_bounds { double origin_reach, origin_coord, dir_norm; } rt_query_bounds;
+#define RT_QUERY_DEVICE       1u
+#define RT_HIT_VALID          1u    /* the ray hit something */
+#define RT_HIT_OUT_OF_BOUNDS  2u    /* beyond a declared bound: not traced */
+#define RT_HIT_NON_FINITE     4u    /* non-finite origin or direction: not traced */
+/* (the statistics record is rt_query_counts: in C a struct typedef and a function cannot share
+ * the name rt_query_stats) */
+typedef struct rt_query_counts {
+    int64_t rays, hits, out_of_bounds, non_finite;
+    int64_t launches;               /* query kernel launches of the call */
+    int32_t reduced;                /* 1: the bounds came from the device reduction */
+    int32_t walk;                   /* 0 general, 1 unified identity, 2 unified transformed, 3 flattened instance tree */
+    rt_query_bounds bounds;         /* the bounds the constants were formed from */
+} rt_query_counts;
+int32_t rt_query_closest(rt_scene* scene, int32_t device_slot, int64_t n, const rt_ray_batch* rays,
+                         const rt_hit_batch* hits, const rt_query_bounds* declared, uint32_t flags, void* stream);
+int32_t rt_query_occluded(rt_scene* scene, int32_t device_slot, int64_t n, const rt_ray_batch* rays, uint8_t* out,
+                          const rt_query_bounds* declared, uint32_t flags, void* stream);
+/* Of the last query on the slot, once its stream has drained (the call waits for nothing). */
+int32_t rt_query_stats(rt_scene* scene, int32_t device_slot, rt_query_counts* out);
+/* Host-only build (no device, as rt_debug_wide_build): the face table, the per-instance object
+ * indices and the triangle records' v0, e1, e2 (9 doubles each).  Call with NULL buffers for the
+ * counts; a buffer that is not NULL must hold what the counts say.  tri_object: per triangle
+ * record the object whose face list it comes from. */
+typedef struct rt_query_tables {
+    int64_t tris, instances;                     /* out */
+    int32_t *face, *tri_object;                  /* per triangle record */
+    double  *verts;                              /* 9 per triangle record */
+    int32_t *inst_object;                        /* per instance */
+} rt_query_tables;
+int32_t rt_debug_query_tables(const rt_scene_desc* desc, uint32_t flags, rt_query_tables* io);
 
 #ifdef __cplusplus
 }

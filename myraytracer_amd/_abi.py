@@ -147,6 +147,36 @@ RT_ERR_OOM = -51
 RT_ERR_CANCELLED = -60
 RT_ERR_STACK = -61
 
+# ---- ray queries (rtcore.h "ray queries"; appended under ABI 5: detected by symbol) ----
+RT_QUERY_DEVICE = 1
+RT_HIT_VALID, RT_HIT_OUT_OF_BOUNDS, RT_HIT_NON_FINITE = 1, 2, 4
+
+
+class rt_ray_batch(C.Structure):
+    _fields_ = [("origin", C.c_void_p), ("dir", C.c_void_p), ("tlimit", C.c_void_p), ("time", C.c_void_p)]
+
+
+class rt_hit_batch(C.Structure):
+    _fields_ = [("t", C.c_void_p), ("uv", C.c_void_p), ("ids", C.c_void_p), ("point", C.c_void_p),
+                ("normal", C.c_void_p), ("flags", C.c_void_p)]
+
+
+class rt_query_bounds(C.Structure):
+    _fields_ = [("origin_reach", C.c_double), ("origin_coord", C.c_double), ("dir_norm", C.c_double)]
+
+
+class rt_query_counts(C.Structure):
+    _fields_ = [("rays", C.c_int64), ("hits", C.c_int64), ("out_of_bounds", C.c_int64), ("non_finite", C.c_int64),
+                ("launches", C.c_int64), ("reduced", C.c_int32), ("walk", C.c_int32), ("bounds", rt_query_bounds)]
+
+
+class rt_query_tables(C.Structure):
+    _fields_ = [("tris", C.c_int64), ("instances", C.c_int64), ("face", c_int32_p), ("tri_object", c_int32_p),
+                ("verts", c_double_p), ("inst_object", c_int32_p)]
+
+
+QUERY_SYMBOLS = ["rt_query_closest", "rt_query_occluded", "rt_query_stats", "rt_debug_query_tables"]
+
 RT_MAT = {"": 0, "default": 0, "mirror": 1, "dielectric": 2, "conductor": 3}
 RT_CAM_LOOKAT, RT_CAM_NEARPLANE = 0, 1
 RT_OBJ_MESH, RT_OBJ_TRIANGLE, RT_OBJ_SPHERE, RT_OBJ_PLANE, RT_OBJ_MESH_INSTANCE = 0, 1, 2, 3, 4
@@ -165,6 +195,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_create_ex", "rt_scene_instance_of_object", "rt_scene_set_instance_transform", "rt_scene_set_camera",
     "rt_scene_instance_bounds", "rt_scene_commit", "rt_debug_wide_build", "rt_debug_wide_read",
     "rt_scene_mesh_vertex_count", "rt_scene_set_mesh_positions", "rt_scene_last_deform_stats",
+    "rt_query_closest", "rt_query_occluded", "rt_query_stats", "rt_debug_query_tables",
 ]
 RT_ABI_VERSION = 5
 
@@ -278,4 +309,15 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.rt_scene_set_mesh_positions.restype = C.c_int32
         lib.rt_scene_last_deform_stats.argtypes = [C.c_void_p, P(rt_deform_stats)]
         lib.rt_scene_last_deform_stats.restype = C.c_int32
+    if hasattr(lib, "rt_query_closest"):   # ray queries (appended under ABI 5: detected by symbol)
+        lib.rt_query_closest.argtypes = [C.c_void_p, C.c_int32, C.c_int64, P(rt_ray_batch), P(rt_hit_batch),
+                                         P(rt_query_bounds), C.c_uint32, C.c_void_p]
+        lib.rt_query_closest.restype = C.c_int32
+        lib.rt_query_occluded.argtypes = [C.c_void_p, C.c_int32, C.c_int64, P(rt_ray_batch), C.c_void_p,
+                                          P(rt_query_bounds), C.c_uint32, C.c_void_p]
+        lib.rt_query_occluded.restype = C.c_int32
+        lib.rt_query_stats.argtypes = [C.c_void_p, C.c_int32, P(rt_query_counts)]
+        lib.rt_query_stats.restype = C.c_int32
+        lib.rt_debug_query_tables.argtypes = [P(rt_scene_desc), C.c_uint32, P(rt_query_tables)]
+        lib.rt_debug_query_tables.restype = C.c_int32
     return lib

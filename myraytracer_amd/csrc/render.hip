@@ -1186,6 +1186,8 @@ __global__ __launch_bounds__(256) void k_occluded_rays(RenderParams P, RayBatch 
 }  // namespace dev
 }  // namespace myrt
 
+#include "query.h"
+
 // ================================================================== host side / C ABI
 using namespace myrt;
 
@@ -1366,6 +1368,16 @@ struct DeviceReplica {
     double* def_vnorm = nullptr; int64_t def_vnorm_cap = 0;
     double* def_part = nullptr; int64_t def_part_cap = 0;
     double* def_out = nullptr; int64_t def_out_cap = 0;
+    // ray queries (query.h; rt_query_closest / rt_query_occluded): the staging of host-array
+    // queries (grown x1.5, the predecessor retired), the slot's query words on the device and
+    // their pinned copy (the three maxima come back through it), the face table (uploaded by the
+    // first query that asks for ids) and what rt_query_stats reports of the last query
+    uint8_t* q_buf = nullptr; int64_t q_cap = 0;
+    unsigned long long* q_words = nullptr;
+    unsigned long long* q_host = nullptr;
+    int32_t* q_face = nullptr;
+    int32_t* q_inst_obj = nullptr;
+    rt_query_counts q_last{};
 };
 
 }  // namespace
@@ -1377,7 +1389,8 @@ enum OptId {
     kOptWide, kOptUnified, kOptUnifiedTransformed, kOptCompactRecords, kOptCompactTris, kOptXcdGroup,
     kOptQueue, kOptQueueLevels, kOptHitlog, kOptNodeshade, kOptLevels, kOptTreePpw, kOptFullFlights,
     kOptDeepCapMb, kOptBatches, kOptZerocopy, kOptSubmitEvents, kOptSubmitCounters, kOptSubmitDma,
-    kOptDebugFailReplica, kOptWideDeltaScale, kOptNodeLists, kOptTileOrder, kOptFit, kOptQueueTail, kOptCount
+    kOptDebugFailReplica, kOptWideDeltaScale, kOptNodeLists, kOptTileOrder, kOptFit, kOptQueueTail, kOptQueryBatch,
+    kOptCount
 };
 // `unsafe` options are test hooks: rt_scene_set_option refuses them (RT_ERR_INVALID_ARG); only the
 // non-production entry point rt_scene_set_unsafe_option sets them (rtcore.h).
@@ -1411,6 +1424,7 @@ static const OptDef kOptDefs[kOptCount] = {
     {"fit", 1, 0, 1},                     // transformed scenes: the flattened instance tree (wide.h fit_walk; 0 = tw_walk)
     {"queue_tail", 2, 0, 15},             // compacted bounce render: levels >= this one in one k_bounce_tail launch (0 = a launch per level;
                                           // C5 one frame 3.49 -> 3.23 ms, pipelined +0.2 %: profiles/r06t_ab_c5_tail.txt, r06u_ab_c5_tail.txt)
+    {"query_batch", 1 << 22, 64, 1 << 30},  // ray queries: rays per launch (and per staging pass of a host-array query)
 };
 
 struct rt_scene {
@@ -1455,7 +1469,8 @@ static int64_t arena_bytes(const BounceArena& a) {
 // device scratch a replica holds now (rt_scene_info.scratch_bytes): grown on demand, kept for reuse
 static int64_t scratch_bytes(const DeviceReplica& r) {
     int64_t b = full_scratch_bytes(r.full) + full_scratch_bytes(r.dev_full) + arena_bytes(r.arena) +
-                arena_bytes(r.dev_arena) + r.deep_cap + r.out_cap_px * 28 + r.wave_times_cap * 24 + r.retired_bytes;
+                arena_bytes(r.dev_arena) + r.deep_cap + r.out_cap_px * 28 + r.wave_times_cap * 24 + r.retired_bytes +
+                r.q_cap + (r.q_words ? dev::kQWords * 8 : 0);
     for (const Flight& f : r.fl) b += full_scratch_bytes(f.full) + arena_bytes(f.arena) + f.stage_px * 28;
     for (const TileOrder& o : r.orders) b += o.n * (int64_t)(sizeof(uint32_t) + 2 * sizeof(unsigned long long));
     return b;
@@ -1533,6 +1548,8 @@ static void free_replica(DeviceReplica& r) {
     (void)hipFree(r.vid); (void)hipFree(r.rec_list); (void)hipFree(r.wide_list); (void)hipFree(r.csr_off); (void)hipFree(r.csr_tri);
     (void)hipFree(r.def_stage); (void)hipFree(r.def_face); (void)hipFree(r.def_vnorm); (void)hipFree(r.def_part);
     (void)hipFree(r.def_out);
+    (void)hipFree(r.q_buf); (void)hipFree(r.q_words); (void)hipFree(r.q_face); (void)hipFree(r.q_inst_obj);
+    if (r.q_host) (void)hipHostFree(r.q_host);
     r.full.release();
     r.dev_full.release();
     (void)hipFree(r.arena.base);
@@ -4044,6 +4061,243 @@ int32_t rt_debug_occluded_rays(rt_scene* s, int32_t slot, int32_t n, const doubl
                                const double* tmax, const double* time, uint8_t* out) {
     if (n > 0 && !out) return fail(RT_ERR_INVALID_ARG, "bad output array");
     return debug_rays(s, slot, n, o, d, tmax, time, nullptr, nullptr, nullptr, nullptr, out);
+}
+
+// ---- ray queries (rtcore.h "ray queries"; query.h) ------------------------------------
+// A host-array query is staged through r.q_buf in passes of at most `m` rays: per ray 17 doubles
+// (o, d, tlimit, time in; t, uv, point, normal out), the four ids and the two byte arrays.
+constexpr int64_t kQueryStageBytes = 17 * 8 + 4 * 4 + 2;
+struct QueryStage {
+    double *o, *d, *tlim, *time, *t, *uv, *point, *normal;
+    int32_t* ids;
+    uint8_t *flags, *occ;
+};
+static QueryStage query_stage(uint8_t* base, int64_t m) {
+    QueryStage q;
+    double* p = (double*)base;
+    q.o = p; p += 3 * m; q.d = p; p += 3 * m; q.tlim = p; p += m; q.time = p; p += m;
+    q.t = p; p += m; q.uv = p; p += 2 * m; q.point = p; p += 3 * m; q.normal = p; p += 3 * m;
+    q.ids = (int32_t*)p;
+    q.flags = (uint8_t*)(q.ids + 4 * m);
+    q.occ = q.flags + m;
+    return q;
+}
+static bool on_device(const void* p, int device) {
+    hipPointerAttribute_t at{};
+    if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return at.type == hipMemoryTypeDevice && at.device == device;
+}
+extern "C++" {
+template <int WALK>
+static void launch_query(bool occluded, unsigned blocks, hipStream_t stream, const RenderParams& P,
+                         const dev::QueryBatch& B) {
+    const size_t lds = (size_t)dev::kLds * kRenderBlock * sizeof(unsigned long long);
+    if (occluded) hipLaunchKernelGGL(dev::k_query_occluded<WALK>, dim3(blocks), dim3(kRenderBlock), lds, stream, P, B);
+    else hipLaunchKernelGGL(dev::k_query_closest<WALK>, dim3(blocks), dim3(kRenderBlock), lds, stream, P, B);
+}
+}  // extern "C++"
+
+static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, const rt_hit_batch* hits,
+                          uint8_t* occ, bool occluded, const rt_query_bounds* declared, uint32_t flags, void* stream_) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
+    if (flags & ~RT_QUERY_DEVICE) return fail(RT_ERR_INVALID_ARG, "unknown flags");
+    if (n < 0 || (n > 0 && (!rays || !rays->origin || !rays->dir))) return fail(RT_ERR_INVALID_ARG, "bad ray arrays");
+    if (occluded && n > 0 && !occ) return fail(RT_ERR_INVALID_ARG, "bad output array");
+    if (declared)
+        for (double b : {declared->origin_reach, declared->origin_coord, declared->dir_norm})
+            if (!(b >= 0.0) || !std::isfinite(b))
+                return fail(RT_ERR_INVALID_ARG, "declared bounds must be finite and not negative");
+    const bool on_dev = (flags & RT_QUERY_DEVICE) != 0;
+    const rt_hit_batch H = (hits && !occluded) ? *hits : rt_hit_batch{};
+    DeviceReplica& r = s->devs[slot];
+    if (on_dev && n > 0) {
+        for (const void* p : {(const void*)rays->origin, (const void*)rays->dir, (const void*)rays->tlimit,
+                              (const void*)rays->time, (const void*)H.t, (const void*)H.uv, (const void*)H.ids,
+                              (const void*)H.point, (const void*)H.normal, (const void*)H.flags, (const void*)occ})
+            if (p && !on_device(p, r.device))
+                return fail(RT_ERR_UNSUPPORTED, "RT_QUERY_DEVICE: not a device pointer on the slot's device");
+    }
+    hipStream_t stream = (hipStream_t)stream_;
+    const HostScene& S = s->host;
+    RenderParams P;
+    int64_t batch = 0;
+    double center[3];
+    {   // prepared under the scene's lock: parameters, options, the slot's query scratch
+        std::lock_guard<std::mutex> lock(s->mu);
+        HIP_TRY(hipSetDevice(r.device));
+        if (n == 0) { r.q_last = rt_query_counts{}; return RT_OK; }
+        if (S.cams.empty()) return fail(RT_ERR_UNSUPPORTED, "the scene has no camera");
+        P = make_params(s, r, 0, 0, 1, nullptr, nullptr);
+        batch = s->opt[kOptQueryBatch];
+        for (int k = 0; k < 3; ++k) center[k] = S.scene_center[k];
+        if (!r.q_words) HIP_TRY(hipMalloc((void**)&r.q_words, dev::kQWords * 8));
+        if (!r.q_host) HIP_TRY(hipHostMalloc((void**)&r.q_host, dev::kQWords * 8, hipHostMallocDefault));
+        if (H.ids && !r.q_face) {     // the face table, on the first query that asks for ids
+            int64_t bytes = 0;
+            int32_t rc = upload(S.face, &r.q_face, bytes);
+            if (rc == RT_OK) rc = upload(S.inst_obj, &r.q_inst_obj, bytes);
+            if (rc != RT_OK) {
+                (void)hipFree(r.q_face); (void)hipFree(r.q_inst_obj);
+                r.q_face = nullptr; r.q_inst_obj = nullptr;
+                return rc;
+            }
+            r.bytes += (int64_t)(S.face.size() + S.inst_obj.size()) * 4;
+        }
+        if (!on_dev && !grow_buf(r, &r.q_buf, r.q_cap, std::min(n, batch) * kQueryStageBytes, 1))
+            return fail(RT_ERR_OOM, "query staging does not fit on the device");
+    }
+    const int64_t m_max = std::min(n, batch);
+    const int64_t launches = (n + batch - 1) / batch;
+    const QueryStage st = on_dev ? QueryStage{} : query_stage(r.q_buf, m_max);
+    HIP_TRY(hipMemsetAsync(r.q_words, 0, dev::kQWords * 8, stream));
+    rt_query_bounds bounds{};
+    bool staged_od = false;              // a one-pass host query uploads its origins and directions once
+    if (declared) {
+        bounds = *declared;
+    } else {
+        for (int64_t base = 0; base < n; base += batch) {
+            const int64_t m = std::min(batch, n - base);
+            const double *o = rays->origin + 3 * base, *d = rays->dir + 3 * base;
+            if (!on_dev) {
+                HIP_TRY(hipMemcpyAsync(st.o, o, (size_t)m * 24, hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(st.d, d, (size_t)m * 24, hipMemcpyHostToDevice, stream));
+                o = st.o; d = st.d;
+                staged_od = launches == 1;
+            }
+            const unsigned blocks = (unsigned)std::max<int64_t>(
+                1, std::min<int64_t>((m + dev::kRayBoundsBlock - 1) / dev::kRayBoundsBlock, (int64_t)r.cus * 8));
+            hipLaunchKernelGGL(dev::k_ray_bounds, dim3(blocks), dim3(dev::kRayBoundsBlock), 0, stream, o, d, m, center[0],
+                               center[1], center[2], r.q_words);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY(hipMemcpyAsync(r.q_host, r.q_words, 3 * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        std::memcpy(&bounds.origin_reach, &r.q_host[dev::kQWordReach], 8);
+        std::memcpy(&bounds.origin_coord, &r.q_host[dev::kQWordCoord], 8);
+        std::memcpy(&bounds.dir_norm, &r.q_host[dev::kQWordNorm], 8);
+    }
+    int walk = 0;
+    {   // the constants of the batch, by the functions every render uses
+        std::lock_guard<std::mutex> lock(s->mu);
+        P.prune_abs = prune_abs_for(S, bounds.origin_reach);
+        P.fast_rcp = fast_rcp_for(S, 2.0 * bounds.dir_norm + 1.0);
+        set_wide(S, r, P, bounds.origin_coord, s->opt[kOptWide] != 0, s->opt[kOptWideDeltaScale], s->opt[kOptFit] != 0);
+        const bool unified = P.has_tlas && s->opt[kOptUnified] != 0;
+        walk = (unified && P.identity) ? 1 : (unified && P.ut) ? (P.fit ? 3 : 2) : 0;   // the render kernels' walk
+        r.q_last = rt_query_counts{};
+        r.q_last.rays = n; r.q_last.launches = launches; r.q_last.reduced = declared ? 0 : 1;
+        r.q_last.walk = walk; r.q_last.bounds = bounds;
+    }
+    for (int64_t base = 0; base < n; base += batch) {
+        const int64_t m = std::min(batch, n - base);
+        dev::QueryBatch B{};
+        B.n = (int32_t)m;
+        B.mask = (rays->tlimit ? dev::kQHasTlim : 0u) | (rays->time ? dev::kQHasTime : 0u) | (declared ? dev::kQCheck : 0u);
+        for (int k = 0; k < 3; ++k) B.center[k] = center[k];
+        B.reach = bounds.origin_reach; B.coord = bounds.origin_coord; B.norm = bounds.dir_norm;
+        B.words = r.q_words; B.face = r.q_face; B.inst_obj = r.q_inst_obj;
+        if (on_dev) {
+            B.o = rays->origin + 3 * base; B.d = rays->dir + 3 * base;
+            B.tlim = rays->tlimit ? rays->tlimit + base : nullptr;
+            B.time = rays->time ? rays->time + base : nullptr;
+            B.t = H.t ? H.t + base : nullptr; B.uv = H.uv ? H.uv + 2 * base : nullptr;
+            B.ids = H.ids ? H.ids + 4 * base : nullptr;
+            B.point = H.point ? H.point + 3 * base : nullptr; B.normal = H.normal ? H.normal + 3 * base : nullptr;
+            B.flags = H.flags ? H.flags + base : nullptr;
+            B.occ = occ ? occ + base : nullptr;
+        } else {
+            if (!staged_od) {
+                HIP_TRY(hipMemcpyAsync(st.o, rays->origin + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice, stream));
+                HIP_TRY(hipMemcpyAsync(st.d, rays->dir + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice, stream));
+            }
+            if (rays->tlimit) HIP_TRY(hipMemcpyAsync(st.tlim, rays->tlimit + base, (size_t)m * 8, hipMemcpyHostToDevice, stream));
+            if (rays->time) HIP_TRY(hipMemcpyAsync(st.time, rays->time + base, (size_t)m * 8, hipMemcpyHostToDevice, stream));
+            B.o = st.o; B.d = st.d; B.tlim = rays->tlimit ? st.tlim : nullptr; B.time = rays->time ? st.time : nullptr;
+            B.t = H.t ? st.t : nullptr; B.uv = H.uv ? st.uv : nullptr; B.ids = H.ids ? st.ids : nullptr;
+            B.point = H.point ? st.point : nullptr; B.normal = H.normal ? st.normal : nullptr;
+            B.flags = H.flags ? st.flags : nullptr; B.occ = occ ? st.occ : nullptr;
+        }
+        const unsigned blocks = (unsigned)((m + kRenderBlock - 1) / kRenderBlock);
+        switch (walk) {
+            case 1: launch_query<dev::kWalkIdentity>(occluded, blocks, stream, P, B); break;
+            case 2: launch_query<dev::kWalkTransformed>(occluded, blocks, stream, P, B); break;
+            case 3: launch_query<dev::kWalkFit>(occluded, blocks, stream, P, B); break;
+            default: launch_query<dev::kWalkGeneral>(occluded, blocks, stream, P, B); break;
+        }
+        HIP_TRY(hipGetLastError());
+        if (!on_dev) {    // results of this pass, before the next pass reuses the staging
+            if (H.t) HIP_TRY(hipMemcpyAsync(H.t + base, st.t, (size_t)m * 8, hipMemcpyDeviceToHost, stream));
+            if (H.uv) HIP_TRY(hipMemcpyAsync(H.uv + 2 * base, st.uv, (size_t)m * 16, hipMemcpyDeviceToHost, stream));
+            if (H.ids) HIP_TRY(hipMemcpyAsync(H.ids + 4 * base, st.ids, (size_t)m * 16, hipMemcpyDeviceToHost, stream));
+            if (H.point) HIP_TRY(hipMemcpyAsync(H.point + 3 * base, st.point, (size_t)m * 24, hipMemcpyDeviceToHost, stream));
+            if (H.normal) HIP_TRY(hipMemcpyAsync(H.normal + 3 * base, st.normal, (size_t)m * 24, hipMemcpyDeviceToHost, stream));
+            if (H.flags) HIP_TRY(hipMemcpyAsync(H.flags + base, st.flags, (size_t)m, hipMemcpyDeviceToHost, stream));
+            if (occ) HIP_TRY(hipMemcpyAsync(occ + base, st.occ, (size_t)m, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipStreamSynchronize(stream));
+        }
+    }
+    return RT_OK;
+}
+
+int32_t rt_query_closest(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, const rt_hit_batch* hits,
+                         const rt_query_bounds* declared, uint32_t flags, void* stream) {
+    return query_impl(s, slot, n, rays, hits, nullptr, false, declared, flags, stream);
+}
+int32_t rt_query_occluded(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, uint8_t* out,
+                          const rt_query_bounds* declared, uint32_t flags, void* stream) {
+    return query_impl(s, slot, n, rays, nullptr, out, true, declared, flags, stream);
+}
+int32_t rt_query_stats(rt_scene* s, int32_t slot, rt_query_counts* out) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
+    if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
+    std::lock_guard<std::mutex> lock(s->mu);
+    DeviceReplica& r = s->devs[slot];
+    *out = r.q_last;
+    if (r.q_words && r.q_last.rays > 0) {
+        unsigned long long w[dev::kQWords];
+        HIP_TRY(hipSetDevice(r.device));
+        HIP_TRY(hipMemcpy(w, r.q_words, sizeof(w), hipMemcpyDeviceToHost));
+        out->hits = (int64_t)w[dev::kQWordHits];
+        out->out_of_bounds = (int64_t)w[dev::kQWordOob];
+        out->non_finite = (int64_t)w[dev::kQWordNonFinite];
+    }
+    return RT_OK;
+}
+
+int32_t rt_debug_query_tables(const rt_scene_desc* desc, uint32_t flags, rt_query_tables* io) {
+    if (!desc) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!io) return fail(RT_ERR_INVALID_ARG, "NULL argument");
+    if (flags & ~(RT_SCENE_DYNAMIC | RT_SCENE_DEFORMABLE)) return fail(RT_ERR_INVALID_ARG, "unknown scene flags");
+    try {
+        HostScene S;
+        S.deformable = (flags & RT_SCENE_DEFORMABLE) != 0;
+        S.dynamic = (flags & RT_SCENE_DYNAMIC) != 0 || S.deformable;
+        S.keep_tri_src = true;
+        std::string err;
+        const int32_t rc = build_host_scene(desc, S, err);
+        if (rc != RT_OK) return fail(rc, err);
+        io->tris = (int64_t)S.tris.size();
+        io->instances = (int64_t)S.insts.size();
+        for (size_t t = 0; t < S.tris.size(); ++t) {
+            if (io->face) io->face[t] = S.face[t];
+            if (io->tri_object) io->tri_object[t] = S.tri_obj[t];
+            if (io->verts)
+                for (int k = 0; k < 3; ++k) {
+                    io->verts[9 * t + k] = S.tris[t].v0[k];
+                    io->verts[9 * t + 3 + k] = S.tris[t].e1[k];
+                    io->verts[9 * t + 6 + k] = S.tris[t].e2[k];
+                }
+        }
+        for (size_t i = 0; i < S.insts.size(); ++i)
+            if (io->inst_object) io->inst_object[i] = S.inst_obj[i];
+        return RT_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    } catch (const std::exception& e) {
+        return fail(RT_ERR_INVALID_ARG, e.what());
+    }
 }
 
 // ---- debug: canonical BVH hashes (tests compare them with the oracle's)

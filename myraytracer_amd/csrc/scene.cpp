@@ -1045,6 +1045,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
 
     // ---- flatten objects (RTContext.swift:120-378)
     std::vector<Tri> triangles;
+    std::vector<int32_t> triFace, triObj;          // per `triangles[]` entry: face within its object, the object
     std::vector<BlasBuild> blases;
     std::vector<InstBuild> insts;
     struct Base { int blas; int material; double M[16]; int obj; };
@@ -1088,6 +1089,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
             t.e1 = sph ? d3(o.radius, 0, 0) : of(o.normal);
             const int64_t gi = (int64_t)triangles.size();
             triangles.push_back(t);
+            triFace.push_back(-1); triObj.push_back(oi);
             BlasBuild bb;
             bb.kind = sph ? kPrimSphere : kPrimPlane;
             bb.smooth = true;                                                // shadingMode .smooth (unused)
@@ -1116,6 +1118,7 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         if (o.kind == RT_OBJ_TRIANGLE) {                                      // RTContext.swift:193-235
             S.n_tris++;
             blases.push_back(singleTriBlas(o));
+            triFace.push_back(0); triObj.push_back(oi);
             InstBuild ib{};
             ib.blas = (int)blases.size() - 1;
             std::memcpy(ib.M, o.transform, sizeof(ib.M));
@@ -1186,6 +1189,8 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         }
         phase("normals");
         triangles.resize(start + triCount);
+        triFace.resize(start + triCount); triObj.resize(start + triCount, oi);
+        for (int64_t t = 0; t < triCount; ++t) triFace[start + t] = (int32_t)t;
         const int TC = std::max(1, std::min<int>(build_threads(), (int)(triCount / 65536)));
         run_chunks(TC, [&](int kc) {                      // independent per triangle
         for (int64_t t = triCount * kc / TC, tEnd = triCount * (kc + 1) / TC; t < tEnd; ++t) {
@@ -1278,6 +1283,8 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
     S.object_inst.assign((size_t)std::max(0, d->num_objects), -1);
     for (size_t i = 0; i < insts.size(); ++i)
         if (insts[i].obj >= 0) S.object_inst[(size_t)insts[i].obj] = (int32_t)i;
+    S.inst_obj.resize(insts.size());
+    for (size_t i = 0; i < insts.size(); ++i) S.inst_obj[i] = (int32_t)insts[i].obj;
 
     phase("flatten");
     // ---- BLAS builds (buildBLASForMesh: maxLeaf 2, SAH, 12 bins; RTContext.swift:430-435)
@@ -1311,6 +1318,8 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
                 r.last = (q == count - 1) ? 1 : 0;
                 r.prim = (int32_t)g;
                 S.tris.push_back(r);
+                S.face.push_back(triFace[g]);
+                if (S.keep_tri_src) S.tri_obj.push_back(triObj[g]);
                 if (S.deformable)
                     for (size_t k = 0; k < 3; ++k)
                         S.def.vid.push_back(3 * (size_t)g + k < triVid.size() ? triVid[3 * (size_t)g + k] : 0);

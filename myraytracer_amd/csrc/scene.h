@@ -127,6 +127,12 @@ struct HostScene {
     std::vector<int32_t> object_blas;      // per scene object: the BLAS an RT_OBJ_MESH produced, or -1
     std::vector<double> inst_bounds;       // 6 per instance: Instance.worldBounds (lo, hi)
     std::vector<int32_t> object_inst;      // per scene object: the instance it produced, or -1
+    // ray queries (query.h): per TriRec, leaf order, the triangle's index in its own object's face
+    // list (-1: a sphere / plane), and per instance the object it came from (-1: a mesh whose id a
+    // MeshInstance took over).  Kept on the host: a replica takes them on its first ids query.
+    std::vector<int32_t> face;
+    std::vector<int32_t> inst_obj;
+    std::vector<int32_t> tri_obj;          // keep_tri_src only: per TriRec the object that gave the face
     int64_t blas_records = 0, tlas_records = 0;
     int64_t max_stack = 0;                 // traversal stack entries the general walk needs
     int64_t max_stack_unified = 0;         // ... and the unified identity walk

@@ -516,6 +516,49 @@ class RayTracerEngine:
             tl.ctypes.data_as(A.c_double_p), tm.ctypes.data_as(A.c_double_p), out.ctypes.data_as(C.POINTER(C.c_uint8))))
         return out.astype(bool)
 
+    # -- ray queries (rt_query_closest / rt_query_occluded)
+    def query_closest(self, origins, dirs, tmin=None, time=None, *, slot: int = 0, want=("t", "uv", "ids"),
+                      bounds=None) -> "RayHits":
+        """Closest hits of caller-given rays through the scene's production walks (rt_query_closest).
+        `origins` / `dirs` are (N, 3) float64: numpy arrays in give numpy arrays out; contiguous
+        float64 torch tensors on the slot's device are used in place, the work is enqueued on
+        torch.cuda.current_stream() and torch tensors come back (with `bounds` given nothing
+        synchronises).  `tmin` / `time` are per-ray arrays of the same kind, or None (0).
+        `want` names the RayHits fields to fill: t, uv, ids, point, normal, flags.
+        `bounds` = (origin_reach, origin_coord, dir_norm) declares the batch's maxima (rays beyond
+        them come back flagged RT_HIT_OUT_OF_BOUNDS, untraced); None lets the device find them."""
+        unknown = set(want) - set(RayHits.FIELDS)
+        if unknown:
+            raise ValueError(f"unknown RayHits fields {sorted(unknown)}")
+        # `keep` holds the arrays the batch points into (converted copies among them) until the call returns
+        rays, n, on_dev, keep, alloc = _query_rays(origins, dirs, tmin, time)
+        hits = RayHits()
+        hb = A.rt_hit_batch()
+        for name, (cols, dt) in RayHits.FIELDS.items():
+            if name in want:
+                a = alloc((n, cols) if cols > 1 else (n,), dt)
+                setattr(hits, name, a)
+                setattr(hb, name, _ptr(a))
+        _check(load_library().rt_query_closest(self._h, int(slot), n, C.byref(rays), C.byref(hb), _bounds(bounds),
+                                               A.RT_QUERY_DEVICE if on_dev else 0, _stream(on_dev)))
+        return hits
+
+    def query_occluded(self, origins, dirs, tmax=None, time=None, *, slot: int = 0, bounds=None):
+        """Any hit of caller-given segments (rt_query_occluded): per ray 0 = free, 1 = blocked, 2 = not
+        traced (beyond the declared `bounds`, or non-finite), as a uint8 numpy array or torch tensor;
+        arguments as query_closest (`tmax` None = +inf)."""
+        rays, n, on_dev, keep, alloc = _query_rays(origins, dirs, tmax, time)    # keep: as in query_closest
+        out = alloc((n,), np.uint8)
+        _check(load_library().rt_query_occluded(self._h, int(slot), n, C.byref(rays), C.c_void_p(_ptr(out)),
+                                                _bounds(bounds), A.RT_QUERY_DEVICE if on_dev else 0, _stream(on_dev)))
+        return out
+
+    def last_query_stats(self, slot: int = 0) -> A.rt_query_counts:
+        """Counts of the last query on `slot` (rt_query_stats); valid once its stream has drained."""
+        st = A.rt_query_counts()
+        _check(load_library().rt_query_stats(self._h, int(slot), C.byref(st)))
+        return st
+
     def bvh_hash(self, instance: int) -> int:
         return int(load_library().rt_debug_bvh_hash(self._h, instance))
 
@@ -575,6 +618,88 @@ def register_host(arr: np.ndarray):
 
 def unregister_host(arr: np.ndarray):
     _check(load_library().rt_host_unregister(C.c_void_p(arr.ctypes.data)))
+
+
+@dataclass
+class RayHits:
+    """What query_closest returns: the fields named in `want`, the others None.  t: +inf on a miss;
+    uv: Moeller-Trumbore u, v; ids: (object, face within that object, instance, material), -1 on a
+    miss; point / normal: world hit point and geometric normal; flags: RT_HIT_* bits."""
+    t: object = None
+    uv: object = None
+    ids: object = None
+    point: object = None
+    normal: object = None
+    flags: object = None
+    FIELDS = {"t": (1, np.float64), "uv": (2, np.float64), "ids": (4, np.int32), "point": (3, np.float64),
+              "normal": (3, np.float64), "flags": (1, np.uint8)}
+
+
+def _ptr(a):
+    return None if a is None else int(a.data_ptr() if hasattr(a, "data_ptr") else a.ctypes.data)
+
+
+def _bounds(b):
+    return None if b is None else C.byref(A.rt_query_bounds(float(b[0]), float(b[1]), float(b[2])))
+
+
+def _stream(on_dev: bool):
+    if not on_dev:
+        return None
+    import torch
+    return C.c_void_p(torch.cuda.current_stream().cuda_stream or None)
+
+
+def _query_rays(origins, dirs, tlim, time):
+    """rt_ray_batch over the caller's arrays: (batch, n, device?, the arrays it points into, an
+    allocator of outputs of the same kind)."""
+    on_dev = hasattr(origins, "data_ptr") and origins.device.type != "cpu"
+    rays = A.rt_ray_batch()
+    if on_dev:
+        import torch
+        n = int(origins.shape[0])
+        for name, a, cols in (("origins", origins, 3), ("dirs", dirs, 3), ("tlimit", tlim, 1), ("time", time, 1)):
+            if a is None and cols == 1:
+                continue
+            if not isinstance(a, torch.Tensor) or a.device != origins.device or a.dtype != torch.float64 or \
+                    not a.is_contiguous() or a.numel() != n * cols:
+                raise ValueError(f"{name}: a contiguous float64 tensor of {n} x {cols} on {origins.device}")
+        keep = (origins, dirs, tlim, time)
+        dt = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8}
+
+        def alloc(shape, dtype):
+            return torch.empty(shape, dtype=dt[dtype], device=origins.device)
+    else:
+        as_np = (lambda a: a.numpy() if hasattr(a, "data_ptr") else a)
+        o = np.ascontiguousarray(as_np(origins), dtype=np.float64).reshape(-1, 3)
+        d = np.ascontiguousarray(as_np(dirs), dtype=np.float64).reshape(-1, 3)
+        n = o.shape[0]
+        if d.shape[0] != n:
+            raise ValueError("origins and dirs differ in length")
+        per_ray = (lambda a: None if a is None else
+                   np.ascontiguousarray(np.broadcast_to(as_np(a), (n,)), dtype=np.float64))
+        keep = (o, d, per_ray(tlim), per_ray(time))
+
+        def alloc(shape, dtype):
+            return np.empty(shape, dtype)
+    rays.origin, rays.dir, rays.tlimit, rays.time = (_ptr(a) for a in keep)
+    return rays, n, on_dev, keep, alloc
+
+
+def query_tables(scene: Scene, flags: int = 0) -> dict:
+    """The face table of a host-only build (rt_debug_query_tables; no device is touched): face and
+    tri_object per triangle record, verts (tris, 9) = v0, e1, e2, inst_object per instance."""
+    lib = load_library()
+    pk = scene.to_desc()
+    io = A.rt_query_tables()
+    _check(lib.rt_debug_query_tables(pk.ptr, flags, C.byref(io)))
+    nt, ni = int(io.tris), int(io.instances)
+    out = {"face": np.zeros(nt, np.int32), "tri_object": np.zeros(nt, np.int32), "verts": np.zeros((nt, 9)),
+           "inst_object": np.zeros(ni, np.int32)}
+    for name, a in out.items():
+        setattr(io, name, a.ctypes.data_as(dict(A.rt_query_tables._fields_)[name]))
+    _check(lib.rt_debug_query_tables(pk.ptr, flags, C.byref(io)))
+    return out
 
 
 def _ray_arrays(origins, dirs, tlim, time):
