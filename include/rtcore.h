@@ -537,7 +537,15 @@ int32_t rt_debug_wide_read(rt_scene* scene, int32_t slot, rt_wide_dump* io);
  * arrays, n rays; o/d: 3 doubles per ray).  rt_debug_trace_rays = intersectTLAS
  * (RTContext.swift:619-720) with tMin: out_t (+inf on a miss), world hit point, world
  * geometric normal (before facing), materialOverride (-1 on a miss).
- * rt_debug_occluded_rays = occludedTLAS (:724-781) with tMax: out[i] = 1 if blocked.   */
+ * rt_debug_occluded_rays = occludedTLAS (:724-781) with tMax: out[i] = 1 if blocked.
+ * Both are host-array ray queries (below) with declared == NULL on the replica's own stream:
+ * rt_query_closest asking for t, point, normal and ids, of which the material column is returned,
+ * and rt_query_occluded with its byte mapped to out[i] = (byte == 1).  So a ray with a non-finite
+ * origin or direction component is not walked and comes back as a miss (t = +inf, zero point and
+ * normal, material -1; occlusion 0); a call counts as the slot's last query for rt_query_stats;
+ * the first rt_debug_trace_rays on a slot uploads the face table, as any query asking for ids
+ * (rt_scene_info.device_bytes grows once); and a scene without a camera is refused
+ * (RT_ERR_UNSUPPORTED), as by the queries.  n == 0 returns RT_OK and touches nothing.       */
 int32_t rt_debug_trace_rays(rt_scene* scene, int32_t slot, int32_t n, const double* o, const double* d,
                             const double* tmin, const double* time, double* out_t, double* out_p,
                             double* out_n, int32_t* out_mat);
@@ -577,7 +585,7 @@ int32_t rt_debug_wave_times(rt_scene* scene, int32_t slot, int32_t camera_index,
  *             the slot's query scratch, and the call returns with the results in them.
  *   declared  NULL: one reduction kernel finds the batch's largest origin distance to the scene
  *             centre, largest |origin coordinate| and largest |d|, which size the pruning margin and
- *             the four-wide walk's widening exactly as the host loop of the debug entry points does;
+ *             the four-wide walk's widening through the functions every render uses;
  *             the call synchronises `stream` once to read them.  Not NULL: the caller's bounds are
  *             used instead and a device query only enqueues (no synchronisation, nothing read back).
  *             A ray beyond any declared bound is NOT traced: its record is a miss with

@@ -34,7 +34,8 @@ struct QueryBatch {
 };
 
 // 0: trace the ray; RT_HIT_NON_FINITE / RT_HIT_OUT_OF_BOUNDS: report it untraced.  The three
-// magnitudes are formed as the host forms them (render.hip dist_to_center, debug_rays).
+// magnitudes are formed term for term as the host forms a camera's (render.hip dist_to_center,
+// make_params).
 __device__ __forceinline__ bool query_finite(const V3& o, const V3& d) {
     return isfinite(o.x) && isfinite(o.y) && isfinite(o.z) && isfinite(d.x) && isfinite(d.y) && isfinite(d.z);
 }

@@ -1136,56 +1136,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MYRT_SHADE_W
 }  // namespace dev
 }  // namespace myrt
 
-namespace myrt {
-namespace dev {
-// Explicit-ray queries (rt_debug_trace_rays / rt_debug_occluded_rays): the render kernels'
-// walks on caller-given rays, one lane per ray.
-struct RayBatch {
-    const double *o, *d, *tlim, *time;
-    double *out_t, *out_p, *out_n;
-    int32_t* out_mat;
-    uint8_t* out_occ;
-    int32_t n, uni;
-};
-__global__ __launch_bounds__(256) void k_trace_rays(RenderParams P, RayBatch B) {
-    extern __shared__ unsigned long long lds_stack[];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B.n) return;
-    MYRT_STACK(st, lds_stack);
-    Counts c{};
-    const V3 o = v3(B.o[3 * i], B.o[3 * i + 1], B.o[3 * i + 2]), d = v3(B.d[3 * i], B.d[3 * i + 1], B.d[3 * i + 2]);
-    const double time = B.time[i];
-    Hit h;
-    h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
-    if (P.has_tlas) {
-        if (B.uni == 1) uni_closest<false>(P, o, d, rcp(d), B.tlim[i], h, st, c);
-        else if (B.uni == 2) walk_closest<false, kWalkTransformed>(P, o, d, rcp(d), B.tlim[i], time, h, st, c);
-        else if (B.uni == 3) walk_closest<false, kWalkFit>(P, o, d, rcp(d), B.tlim[i], time, h, st, c);
-        else intersect_closest<false>(P, o, d, rcp(d), B.tlim[i], time, h, st, c);
-    }
-    V3 p = v3(0, 0, 0), n = v3(0, 0, 0);
-    if (h.inst >= 0) hit_geometry<false>(P, o, d, time, h, p, n, c);
-    B.out_t[i] = h.inst >= 0 ? h.t : DINF;
-    B.out_p[3 * i] = p.x; B.out_p[3 * i + 1] = p.y; B.out_p[3 * i + 2] = p.z;
-    B.out_n[3 * i] = n.x; B.out_n[3 * i + 1] = n.y; B.out_n[3 * i + 2] = n.z;
-    B.out_mat[i] = h.inst >= 0 ? P.insts[h.inst].material : -1;
-}
-__global__ __launch_bounds__(256) void k_occluded_rays(RenderParams P, RayBatch B) {
-    extern __shared__ unsigned long long lds_stack[];
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B.n) return;
-    MYRT_STACK(st, lds_stack);
-    Counts c{};
-    const V3 o = v3(B.o[3 * i], B.o[3 * i + 1], B.o[3 * i + 2]), d = v3(B.d[3 * i], B.d[3 * i + 1], B.d[3 * i + 2]);
-    const bool hit = B.uni == 1 ? uni_occluded<false>(P, o, d, B.tlim[i], st, c)
-                     : B.uni == 2 ? walk_occluded<false, kWalkTransformed, true, false>(P, o, d, B.tlim[i], B.time[i], st, c)
-                     : B.uni == 3 ? walk_occluded<false, kWalkFit, true, false>(P, o, d, B.tlim[i], B.time[i], st, c)
-                           : occluded<false>(P, o, d, B.tlim[i], B.time[i], st, c);
-    B.out_occ[i] = hit ? 1 : 0;
-}
-}  // namespace dev
-}  // namespace myrt
-
 #include "query.h"
 
 // ================================================================== host side / C ABI
@@ -1827,6 +1777,16 @@ static void set_wide(const HostScene& S, const DeviceReplica& r, RenderParams& P
     P.fit_root = has_fit ? S.fit_root : -1;
     P.fit = (P.wide && has_fit && fit) ? 1 : 0;
 }
+// The constants a batch of rays is traced under (a render's camera rays, a query's rays): the
+// pruning margin from the origins' largest distance to the scene centre, fast_rcp from
+// `rcp_dmax`, which is the argument of fast_rcp_for (a bound on the |d| the triangle tests see, not
+// the batch's largest norm), and the four-wide walk's widening from the largest |origin coordinate|.
+static void set_ray_bounds(const rt_scene* s, const DeviceReplica& r, RenderParams& P, double origin_reach,
+                           double origin_coord, double rcp_dmax) {
+    P.prune_abs = prune_abs_for(s->host, origin_reach);
+    P.fast_rcp = fast_rcp_for(s->host, rcp_dmax);
+    set_wide(s->host, r, P, origin_coord, s->opt[kOptWide] != 0, s->opt[kOptWideDeltaScale], s->opt[kOptFit] != 0);
+}
 
 static RenderParams make_params(const rt_scene* s, const DeviceReplica& r, int32_t cam, int32_t first, int32_t step,
                                 double* out_rgb, uint8_t* out_rgba8) {
@@ -1855,9 +1815,11 @@ static RenderParams make_params(const rt_scene* s, const DeviceReplica& r, int32
     {
         const rt_camera& cam0 = S.cams[cam];
         const double ce[3] = {cam0.position.x, cam0.position.y, cam0.position.z};
-        P.prune_abs = prune_abs_for(S, dist_to_center(S, ce) + std::fabs(cam0.aperture_size));
+        const double lens = std::fabs(cam0.aperture_size);
+        // rendered directions are normalized (|d| <= 1 + 2^-50): 2.0 for fast_rcp_for
+        set_ray_bounds(s, r, P, dist_to_center(S, ce) + lens,
+                       std::max({std::fabs(ce[0]), std::fabs(ce[1]), std::fabs(ce[2])}) + lens, 2.0);
     }
-    P.fast_rcp = fast_rcp_for(S, 2.0);   // rendered directions are normalized (|d| <= 1 + 2^-50)
     for (int k = 0; k < 3; ++k) { P.background[k] = S.background[k]; P.ambient[k] = S.ambient[k]; }
     P.max_depth = S.max_depth;
     P.chunk_first = first; P.chunk_step = step;
@@ -1881,12 +1843,6 @@ static RenderParams make_params(const rt_scene* s, const DeviceReplica& r, int32
     P.jitter = r.jitter;
     P.num_alights = (int32_t)S.alights.size();
     P.has_special = S.has_special ? 1 : 0;
-    {
-        const rt_camera& cam0 = S.cams[cam];
-        const double ce[3] = {cam0.position.x, cam0.position.y, cam0.position.z};
-        set_wide(S, r, P, std::max({std::fabs(ce[0]), std::fabs(ce[1]), std::fabs(ce[2])}) + std::fabs(cam0.aperture_size),
-                 s->opt[kOptWide] != 0, s->opt[kOptWideDeltaScale], s->opt[kOptFit] != 0);
-    }
     return P;
 }
 
@@ -1935,6 +1891,25 @@ static void clist_launch(const RenderParams& P, int level, unsigned bits, int wo
     hipLaunchKernelGGL(dev::k_ccount, grid, dim3(dev::kCListThreads), 0, stream, P, level, bits);
     hipLaunchKernelGGL(dev::k_clist, grid, dim3(dev::kCListThreads), 0, stream, P, level, bits, word);
 }
+// The walk: identity scenes walk TLAS + BLAS as one tree; other scenes the unified transformed
+// walk (per-instance ray switches), or the nested general walk when the stack bound does not
+// allow one stack or for counting launches (reference-order counting needs the general walk)
+static int select_walk(const rt_scene* s, const RenderParams& P, bool count) {
+    const bool unified = P.has_tlas && !P.count_ref && s->opt[kOptUnified] != 0;
+    return (unified && P.identity) ? dev::kWalkIdentity
+           : (unified && P.ut && !count) ? (P.fit ? dev::kWalkFit : dev::kWalkTransformed) : dev::kWalkGeneral;
+}
+// rt_query_counts::walk (rtcore.h) is documented as these numbers
+static_assert(dev::kWalkGeneral == 0 && dev::kWalkIdentity == 1 && dev::kWalkTransformed == 2 && dev::kWalkFit == 3,
+              "rt_query_counts::walk reports the dev::kWalk* values");
+// M_(W) with W the compile-time constant equal to the local `walk`
+#define MYRT_BY_WALK(M_)                                                    \
+    do {                                                                    \
+        if (walk == dev::kWalkIdentity) M_(dev::kWalkIdentity);             \
+        else if (walk == dev::kWalkFit) M_(dev::kWalkFit);                  \
+        else if (walk == dev::kWalkTransformed) M_(dev::kWalkTransformed);  \
+        else M_(dev::kWalkGeneral);                                         \
+    } while (0)
 static int32_t launch_full(const rt_scene* s, DeviceReplica& r, FullScratch& fs, RenderParams P, hipStream_t stream,
                            bool count, bool dielectric, bool rough) {
     const int bt = kRenderBlock;
@@ -1956,16 +1931,7 @@ static int32_t launch_full(const rt_scene* s, DeviceReplica& r, FullScratch& fs,
         }
         P.deep = r.deep;
     }
-    const bool unified = P.has_tlas && !P.count_ref && s->opt[kOptUnified] != 0;
-    const int walk = (unified && P.identity) ? dev::kWalkIdentity
-                     : (unified && P.ut && !count) ? (P.fit ? dev::kWalkFit : dev::kWalkTransformed) : dev::kWalkGeneral;
-#define MYRT_BY_WALK(M_)                                                    \
-    do {                                                                    \
-        if (walk == dev::kWalkIdentity) M_(dev::kWalkIdentity);             \
-        else if (walk == dev::kWalkFit) M_(dev::kWalkFit);                  \
-        else if (walk == dev::kWalkTransformed) M_(dev::kWalkTransformed);  \
-        else M_(dev::kWalkGeneral);                                         \
-    } while (0)
+    const int walk = select_walk(s, P, count);
     // Area-light frames need the events passes (jitterIndex prefixes); dielectric frames without
     // area lights take the same level passes + node shading when they apply (no rough
     // material, whole trees logged), else render_full alone walks and shades every tree.
@@ -2134,7 +2100,6 @@ static int32_t launch_full(const rt_scene* s, DeviceReplica& r, FullScratch& fs,
 #undef MYRT_RF0
         }
     }
-#undef MYRT_BY_WALK
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }
@@ -2333,20 +2298,8 @@ static int32_t launch(const rt_scene* s, DeviceReplica& r, const RenderParams& P
     const size_t lds = (size_t)dev::kLds * bt * sizeof(unsigned long long) +
                        (size_t)(dev::kPixSlots + dev::kParkSlots) * bt * sizeof(double);
     const bool bounce = scene_has_bounce(s->host) && P.max_depth > 0;
-    // The walk: identity scenes walk TLAS + BLAS as one tree; other scenes the unified transformed
-    // walk (per-instance ray switches), or the nested general walk when the stack bound does not
-    // allow one stack or for counting launches (reference-order counting needs the general walk)
-    const bool unified = P.has_tlas && !P.count_ref && s->opt[kOptUnified] != 0;
-    const int walk = (unified && P.identity) ? dev::kWalkIdentity
-                     : (unified && P.ut && !count) ? (P.fit ? dev::kWalkFit : dev::kWalkTransformed) : dev::kWalkGeneral;
+    const int walk = select_walk(s, P, count);
 #define MYRT_LAUNCH(C_, B_, W_) hipLaunchKernelGGL((dev::render_kernel<C_, B_, W_>), grid, block, lds, stream, P)
-#define MYRT_BY_WALK(M_)                                                    \
-    do {                                                                    \
-        if (walk == dev::kWalkIdentity) M_(dev::kWalkIdentity);             \
-        else if (walk == dev::kWalkFit) M_(dev::kWalkFit);                  \
-        else if (walk == dev::kWalkTransformed) M_(dev::kWalkTransformed);  \
-        else M_(dev::kWalkGeneral);                                         \
-    } while (0)
     if (bounce && !count && queue_arena(s, r, arena, P, (int64_t)grid.x * (bt / 64), stream)) {
         // primary + shadow rays of every pixel in the spill-free primary instantiation, then per
         // level the level's rays in coherent batches (k_bounce), then the need (k_queue_done)
@@ -2388,7 +2341,6 @@ static int32_t launch(const rt_scene* s, DeviceReplica& r, const RenderParams& P
 #undef MYRT_B0
         if (measuring) HIP_TRY(hipEventRecord(measuring->ev, stream));
     }
-#undef MYRT_BY_WALK
 #undef MYRT_LAUNCH
     HIP_TRY(hipGetLastError());
     return RT_OK;
@@ -3976,93 +3928,6 @@ int32_t rt_debug_wide_read(rt_scene* s, int32_t slot, rt_wide_dump* io) {
     }
 }
 
-// ---- debug: explicit rays through the render kernels' traversal
-static int32_t debug_rays(rt_scene* s, int32_t slot, int32_t n, const double* o, const double* d, const double* tl,
-                          const double* time, double* out_t, double* out_p, double* out_n, int32_t* out_mat,
-                          uint8_t* out_occ) {
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
-    if (n < 0 || (n > 0 && (!o || !d || !tl || !time))) return fail(RT_ERR_INVALID_ARG, "bad ray arrays");
-    if (n == 0) return RT_OK;
-    std::lock_guard<std::mutex> lock(s->mu);
-    DeviceReplica& r = s->devs[slot];
-    HIP_TRY(hipSetDevice(r.device));
-    RenderParams P = make_params(s, r, 0, 0, 1, nullptr, nullptr);
-    {   // margin for these rays' own origins
-        double od = 0.0;
-        double dm = 0.0;
-        for (int32_t k = 0; k < n; ++k) {
-            od = std::max(od, dist_to_center(s->host, o + 3 * (size_t)k));
-            const double* dk = d + 3 * (size_t)k;
-            const double dn = std::sqrt(dk[0] * dk[0] + dk[1] * dk[1] + dk[2] * dk[2]);
-            dm = std::isfinite(dn) ? std::max(dm, dn) : HUGE_VAL;
-        }
-        P.prune_abs = prune_abs_for(s->host, od);
-        P.fast_rcp = fast_rcp_for(s->host, 2.0 * dm + 1.0);
-        double oc = 0.0;                      // the wide walk's widening for these origins
-        for (int32_t k = 0; k < 3 * n; ++k) oc = std::isfinite(o[k]) ? std::max(oc, std::fabs(o[k])) : HUGE_VAL;
-        set_wide(s->host, r, P, oc, s->opt[kOptWide] != 0, s->opt[kOptWideDeltaScale], s->opt[kOptFit] != 0);
-    }
-    dev::RayBatch B{};
-    B.n = n;
-    const bool unified = P.has_tlas && s->opt[kOptUnified] != 0;
-    B.uni = (unified && P.identity) ? 1 : (unified && P.ut) ? (P.fit ? 3 : 2) : 0;   // the render kernels' walk
-    std::vector<void*> allocs;
-    auto dalloc = [&](size_t bytes, void** p) -> int32_t {
-        HIP_TRY(hipMalloc(p, std::max<size_t>(bytes, 8)));
-        allocs.push_back(*p);
-        return RT_OK;
-    };
-    int32_t rc = RT_OK;
-    double *dO, *dD, *dL, *dT;
-    if ((rc = dalloc((size_t)n * 24, (void**)&dO)) || (rc = dalloc((size_t)n * 24, (void**)&dD)) ||
-        (rc = dalloc((size_t)n * 8, (void**)&dL)) || (rc = dalloc((size_t)n * 8, (void**)&dT))) {
-        for (void* p : allocs) (void)hipFree(p);
-        return rc;
-    }
-    HIP_TRY(hipMemcpy(dO, o, (size_t)n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dD, d, (size_t)n * 24, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dL, tl, (size_t)n * 8, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dT, time, (size_t)n * 8, hipMemcpyHostToDevice));
-    B.o = dO; B.d = dD; B.tlim = dL; B.time = dT;
-    const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    const size_t lds = (size_t)dev::kLds * 256 * sizeof(unsigned long long);
-    if (out_occ) {
-        if ((rc = dalloc((size_t)n, (void**)&B.out_occ)) != RT_OK) { for (void* p : allocs) (void)hipFree(p); return rc; }
-        hipLaunchKernelGGL(dev::k_occluded_rays, grid, block, lds, r.stream, P, B);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(r.stream));
-        HIP_TRY(hipMemcpy(out_occ, B.out_occ, (size_t)n, hipMemcpyDeviceToHost));
-    } else {
-        if ((rc = dalloc((size_t)n * 8, (void**)&B.out_t)) || (rc = dalloc((size_t)n * 24, (void**)&B.out_p)) ||
-            (rc = dalloc((size_t)n * 24, (void**)&B.out_n)) || (rc = dalloc((size_t)n * 4, (void**)&B.out_mat))) {
-            for (void* p : allocs) (void)hipFree(p);
-            return rc;
-        }
-        hipLaunchKernelGGL(dev::k_trace_rays, grid, block, lds, r.stream, P, B);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(r.stream));
-        HIP_TRY(hipMemcpy(out_t, B.out_t, (size_t)n * 8, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_p, B.out_p, (size_t)n * 24, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_n, B.out_n, (size_t)n * 24, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(out_mat, B.out_mat, (size_t)n * 4, hipMemcpyDeviceToHost));
-    }
-    for (void* p : allocs) (void)hipFree(p);
-    return RT_OK;
-}
-
-int32_t rt_debug_trace_rays(rt_scene* s, int32_t slot, int32_t n, const double* o, const double* d,
-                            const double* tmin, const double* time, double* out_t, double* out_p, double* out_n,
-                            int32_t* out_mat) {
-    if (n > 0 && (!out_t || !out_p || !out_n || !out_mat)) return fail(RT_ERR_INVALID_ARG, "bad output arrays");
-    return debug_rays(s, slot, n, o, d, tmin, time, out_t, out_p, out_n, out_mat, nullptr);
-}
-int32_t rt_debug_occluded_rays(rt_scene* s, int32_t slot, int32_t n, const double* o, const double* d,
-                               const double* tmax, const double* time, uint8_t* out) {
-    if (n > 0 && !out) return fail(RT_ERR_INVALID_ARG, "bad output array");
-    return debug_rays(s, slot, n, o, d, tmax, time, nullptr, nullptr, nullptr, nullptr, out);
-}
-
 // ---- ray queries (rtcore.h "ray queries"; query.h) ------------------------------------
 // A host-array query is staged through r.q_buf in passes of at most `m` rays: per ray 17 doubles
 // (o, d, tlimit, time in; t, uv, point, normal out), the four ids and the two byte arrays.
@@ -4087,15 +3952,6 @@ static bool on_device(const void* p, int device) {
     if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return false; }
     return at.type == hipMemoryTypeDevice && at.device == device;
 }
-extern "C++" {
-template <int WALK>
-static void launch_query(bool occluded, unsigned blocks, hipStream_t stream, const RenderParams& P,
-                         const dev::QueryBatch& B) {
-    const size_t lds = (size_t)dev::kLds * kRenderBlock * sizeof(unsigned long long);
-    if (occluded) hipLaunchKernelGGL(dev::k_query_occluded<WALK>, dim3(blocks), dim3(kRenderBlock), lds, stream, P, B);
-    else hipLaunchKernelGGL(dev::k_query_closest<WALK>, dim3(blocks), dim3(kRenderBlock), lds, stream, P, B);
-}
-}  // extern "C++"
 
 static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, const rt_hit_batch* hits,
                           uint8_t* occ, bool occluded, const rt_query_bounds* declared, uint32_t flags, void* stream_) {
@@ -4180,11 +4036,8 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
     int walk = 0;
     {   // the constants of the batch, by the functions every render uses
         std::lock_guard<std::mutex> lock(s->mu);
-        P.prune_abs = prune_abs_for(S, bounds.origin_reach);
-        P.fast_rcp = fast_rcp_for(S, 2.0 * bounds.dir_norm + 1.0);
-        set_wide(S, r, P, bounds.origin_coord, s->opt[kOptWide] != 0, s->opt[kOptWideDeltaScale], s->opt[kOptFit] != 0);
-        const bool unified = P.has_tlas && s->opt[kOptUnified] != 0;
-        walk = (unified && P.identity) ? 1 : (unified && P.ut) ? (P.fit ? 3 : 2) : 0;   // the render kernels' walk
+        set_ray_bounds(s, r, P, bounds.origin_reach, bounds.origin_coord, 2.0 * bounds.dir_norm + 1.0);
+        walk = select_walk(s, P, false);      // the render kernels' walk
         r.q_last = rt_query_counts{};
         r.q_last.rays = n; r.q_last.launches = launches; r.q_last.reduced = declared ? 0 : 1;
         r.q_last.walk = walk; r.q_last.bounds = bounds;
@@ -4218,13 +4071,14 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
             B.point = H.point ? st.point : nullptr; B.normal = H.normal ? st.normal : nullptr;
             B.flags = H.flags ? st.flags : nullptr; B.occ = occ ? st.occ : nullptr;
         }
-        const unsigned blocks = (unsigned)((m + kRenderBlock - 1) / kRenderBlock);
-        switch (walk) {
-            case 1: launch_query<dev::kWalkIdentity>(occluded, blocks, stream, P, B); break;
-            case 2: launch_query<dev::kWalkTransformed>(occluded, blocks, stream, P, B); break;
-            case 3: launch_query<dev::kWalkFit>(occluded, blocks, stream, P, B); break;
-            default: launch_query<dev::kWalkGeneral>(occluded, blocks, stream, P, B); break;
-        }
+        const dim3 grid((unsigned)((m + kRenderBlock - 1) / kRenderBlock)), block(kRenderBlock);
+        const size_t lds = (size_t)dev::kLds * kRenderBlock * sizeof(unsigned long long);
+#define MYRT_QOCC(W_) hipLaunchKernelGGL((dev::k_query_occluded<W_>), grid, block, lds, stream, P, B)
+#define MYRT_QHIT(W_) hipLaunchKernelGGL((dev::k_query_closest<W_>), grid, block, lds, stream, P, B)
+        if (occluded) MYRT_BY_WALK(MYRT_QOCC);
+        else MYRT_BY_WALK(MYRT_QHIT);
+#undef MYRT_QHIT
+#undef MYRT_QOCC
         HIP_TRY(hipGetLastError());
         if (!on_dev) {    // results of this pass, before the next pass reuses the staging
             if (H.t) HIP_TRY(hipMemcpyAsync(H.t + base, st.t, (size_t)m * 8, hipMemcpyDeviceToHost, stream));
@@ -4247,6 +4101,45 @@ int32_t rt_query_closest(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batc
 int32_t rt_query_occluded(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, uint8_t* out,
                           const rt_query_bounds* declared, uint32_t flags, void* stream) {
     return query_impl(s, slot, n, rays, nullptr, out, true, declared, flags, stream);
+}
+#undef MYRT_BY_WALK
+
+// ---- debug: explicit rays (rtcore.h).  The test hooks are host-array queries with reduced bounds on
+// the replica's own stream, repacked: the material column of the ids, the occlusion byte as 0 / 1.
+static int32_t debug_ray_args(const rt_scene* s, int32_t slot, int32_t n, const double* o, const double* d,
+                              const double* tl, const double* time) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
+    if (n < 0 || (n > 0 && (!o || !d || !tl || !time))) return fail(RT_ERR_INVALID_ARG, "bad ray arrays");
+    return RT_OK;
+}
+int32_t rt_debug_trace_rays(rt_scene* s, int32_t slot, int32_t n, const double* o, const double* d,
+                            const double* tmin, const double* time, double* out_t, double* out_p, double* out_n,
+                            int32_t* out_mat) {
+    if (n > 0 && (!out_t || !out_p || !out_n || !out_mat)) return fail(RT_ERR_INVALID_ARG, "bad output arrays");
+    int32_t rc = debug_ray_args(s, slot, n, o, d, tmin, time);
+    if (rc != RT_OK || n == 0) return rc;
+    try {
+        std::vector<int32_t> ids(4 * (size_t)n);
+        const rt_ray_batch rays{o, d, tmin, time};
+        rt_hit_batch hits{};
+        hits.t = out_t; hits.point = out_p; hits.normal = out_n; hits.ids = ids.data();
+        rc = query_impl(s, slot, n, &rays, &hits, nullptr, false, nullptr, 0u, s->devs[slot].stream);
+        for (int32_t i = 0; rc == RT_OK && i < n; ++i) out_mat[i] = ids[4 * (size_t)i + 3];
+        return rc;
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    }
+}
+int32_t rt_debug_occluded_rays(rt_scene* s, int32_t slot, int32_t n, const double* o, const double* d,
+                               const double* tmax, const double* time, uint8_t* out) {
+    if (n > 0 && !out) return fail(RT_ERR_INVALID_ARG, "bad output array");
+    int32_t rc = debug_ray_args(s, slot, n, o, d, tmax, time);
+    if (rc != RT_OK || n == 0) return rc;
+    const rt_ray_batch rays{o, d, tmax, time};
+    rc = query_impl(s, slot, n, &rays, nullptr, out, true, nullptr, 0u, s->devs[slot].stream);
+    for (int32_t i = 0; rc == RT_OK && i < n; ++i) out[i] = out[i] == 1 ? 1 : 0;   // 2 = not traced
+    return rc;
 }
 int32_t rt_query_stats(rt_scene* s, int32_t slot, rt_query_counts* out) {
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");

@@ -498,7 +498,8 @@ class RayTracerEngine:
 
     def trace_rays(self, origins, dirs, tmin=None, time=None, slot: int = 0):
         """Closest hits of explicit rays through the render kernels' traversal
-        (rt_debug_trace_rays): returns t (+inf = miss), world point, world normal, material."""
+        (rt_debug_trace_rays, a thin caller of the ray-query path: query_closest on host arrays):
+        returns t (+inf = miss), world point, world normal, material."""
         o, d, n, tl, tm = _ray_arrays(origins, dirs, tmin, time)
         t = np.empty(n); p = np.empty((n, 3)); nn = np.empty((n, 3)); mat = np.empty(n, np.int32)
         _check(load_library().rt_debug_trace_rays(
@@ -508,7 +509,8 @@ class RayTracerEngine:
         return t, p, nn, mat
 
     def occluded_rays(self, origins, dirs, tmax, time=None, slot: int = 0):
-        """Any-hit of explicit segments (rt_debug_occluded_rays): bool per ray."""
+        """Any-hit of explicit segments (rt_debug_occluded_rays, a thin caller of the ray-query
+        path: query_occluded on host arrays): bool per ray."""
         o, d, n, tl, tm = _ray_arrays(origins, dirs, tmax, time)
         out = np.empty(n, np.uint8)
         _check(load_library().rt_debug_occluded_rays(

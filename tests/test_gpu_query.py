@@ -3,7 +3,8 @@ on caller-given rays from host arrays and from torch tensors on the device, with
 
 The bar is the one the explicit-ray tests hold: t, point, normal and material bit-identical to the
 oracle's intersectTLAS, occlusion identical to occludedTLAS, on every walk the options select; the
-host path, the device path and engine.trace_rays agree bit for bit.  On top of that: the ids and
+host path and the device path agree bit for bit, and engine.trace_rays / occluded_rays (the test
+hooks, which call the query path) repack the same answer faithfully.  On top of that: the ids and
 barycentrics name the triangle that was hit; the device-side reduction of the batch's bounds sizes
 the four-wide walk's widening (teeth: wide_delta_scale = 0 mismatches); declared bounds flag
 exactly the rays beyond them; shapes, optional outputs, moving and deforming scenes, two replicas,
@@ -81,6 +82,9 @@ def _assert_oracle(h, ref):
 
 
 def _assert_debug(eng, h, O, D, tmin=None, time=None):
+    """rt_debug_trace_rays is a thin caller of the query path: this checks that its repacking (t,
+    point, normal, the material column of the ids) is faithful, not two kernels against each
+    other.  Parity of the query path itself rests on _assert_oracle."""
     tg, pg, ng, mg = eng.trace_rays(O, D, tmin, time)
     assert _same(h.t, tg) and _same(h.point, pg) and _same(h.normal, ng) and np.array_equal(h.ids[:, 3], mg)
 

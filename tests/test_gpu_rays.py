@@ -356,6 +356,38 @@ def test_equal_t_ties_between_transformed_instances(walk):
         assert st.rewalked == 0
 
 
+@pytest.mark.parametrize("scene", ["transformed", "identity"])
+def test_hooks_across_staging_passes(scene):
+    """trace_rays / occluded_rays are host-array ray queries, staged in passes of `query_batch`
+    rays: 200 rays at its minimum, 64, are three full passes and one of 8, and every ray still
+    gets the oracle's answer bit for bit (each pass reuses the staging of the one before)."""
+    if scene == "transformed":
+        sc = _transformed_instances()
+        O, D = _ray_set(np.array([0.0, 0.0, 0.0]), 4.0, 176, 23)
+        tmax = np.random.RandomState(6).uniform(0.1, 8.0, size=len(O))
+    else:
+        sc = scenes.scaled(scenes.scene_c2(inline=True), 8, 8)
+        O, D = _ray_set(np.array([0.0, 0.0, 0.0]), 2.5, 176, 7)
+        tmax = np.random.RandomState(3).uniform(0.05, 4.0, size=len(O))
+    assert len(O) == 200
+    orc = oracle.OracleScene(sc)
+    to, po, no, mo = orc.trace_rays(O, D)
+    occ = orc.occluded_rays(O, D, tmax)
+    hit = np.isfinite(to)
+    assert 0.05 < hit.mean() < 0.98 and 0.05 < occ.mean() < 0.98
+    eng = M.RayTracerEngine(sc)
+    eng.set_option("query_batch", 64)
+    tg, pg, ng, mg = eng.trace_rays(O, D)
+    assert eng.last_query_stats().launches == 4
+    assert np.array_equal(tg, to), f"t differs on {int((tg != to).sum())} of {len(to)} rays"
+    assert np.array_equal(mg, mo)
+    assert np.array_equal(pg[hit], po[hit]) and np.array_equal(ng[hit], no[hit])
+    g = eng.occluded_rays(O, D, tmax)
+    assert eng.last_query_stats().launches == 4
+    eng.close()
+    assert np.array_equal(g, occ), f"occlusion differs on {int((g != occ).sum())} rays"
+
+
 def test_fast_reciprocal_is_ieee_division():
     """device.h rcp_rn (1/det of the triangle tests when RenderParams::fast_rcp holds) equals
     IEEE 1.0/x bit for bit over its range 2^-700 <= |x| <= 2^1000: random mantissas at every

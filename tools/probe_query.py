@@ -6,7 +6,8 @@ C3 (1.02M triangles, the four-wide identity walk), three sets of 2^22 rays:
   shuffled  the same rays in random order
   random    uniformly random origins in the scene box, random directions
 each through rt_query_closest (want t, uv, ids) and rt_query_occluded (tMax = +inf), as:
-  debug           engine.trace_rays / occluded_rays (rt_debug_*): what a caller had before
+  debug           engine.trace_rays / occluded_rays (rt_debug_*): what a caller had before (the
+                  hooks call the host-array query now: this row is `host` plus their repacking)
   host            numpy arrays in, numpy arrays out (staged through the slot's query scratch)
   device          torch tensors on the GPU, bounds reduced on the device (one synchronisation)
   device+bounds   ... bounds declared (the call only enqueues)
