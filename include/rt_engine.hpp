@@ -168,9 +168,16 @@ public:
         check(rt_scene_set_camera(scene_, index, &camera));
         cams_.at((size_t)index) = camera;
     }
-    rt_commit_stats commit() {
+    /* commit(true) also builds the flattened instance tree again on the device for the new pose
+     * (RT_COMMIT_REBUILD_FIT); lastRebuildStats() says what the last commit did for it. */
+    rt_commit_stats commit(bool rebuild = false) {
         rt_commit_stats st{};
-        check(rt_scene_commit(scene_, &st));
+        check(rebuild ? rt_scene_commit_ex(scene_, RT_COMMIT_REBUILD_FIT, &st) : rt_scene_commit(scene_, &st));
+        return st;
+    }
+    rt_rebuild_stats lastRebuildStats() const {
+        rt_rebuild_stats st{};
+        check(rt_scene_last_rebuild_stats(scene_, &st));
         return st;
     }
     /* Deforming meshes (an engine built with `deformable`, which implies `dynamic`): BVHBuilder.refit

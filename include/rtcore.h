@@ -56,7 +56,8 @@
  *      Appended later without moving the version, as the rt_debug_wide_* pair was (callers detect
  *      them by symbol): deforming meshes - RT_SCENE_DEFORMABLE, rt_scene_mesh_vertex_count,
  *      rt_scene_set_mesh_positions, rt_scene_last_deform_stats; ray queries - rt_query_closest,
- *      rt_query_occluded, rt_query_stats. */
+ *      rt_query_occluded, rt_query_stats; the flattened instance tree rebuilt at a commit -
+ *      rt_scene_commit_ex with RT_COMMIT_REBUILD_FIT, rt_scene_last_rebuild_stats. */
 #define RT_ABI_VERSION 5
 
 #ifdef __cplusplus
@@ -231,7 +232,10 @@ int32_t rt_scene_info_get(const rt_scene* scene, rt_scene_info* out);
  *                                    and changes nothing.  RT_ERR_UNSUPPORTED without
  *                                    RT_SCENE_DYNAMIC; RT_ERR_INVALID_ARG (nothing changed, the
  *                                    staged transforms dropped) when a transform puts an instance
- *                                    beyond 1e30.
+ *                                    beyond 1e30.  Every tree keeps the topology of the pose the
+ *                                    scene was created at; rt_scene_commit_ex (below, "rebuilding
+ *                                    the flattened instance tree") can build the one tree whose
+ *                                    topology is free again for the committed pose.
  * rt_scene_commit and rt_scene_set_camera return RT_ERR_BUSY, and change nothing, while a render
  * submitted with rt_render_submit has not been waited for.  Renders enqueued with rt_render_device
  * on caller streams are the caller's to order: synchronise those streams before a commit or a
@@ -299,6 +303,57 @@ typedef struct rt_deform_stats {
 } rt_deform_stats;
 int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);   /* of the last commit */
 
+/* ---- rebuilding the flattened instance tree (appended under ABI 5; detect by symbol) -----------
+ * A commit keeps the topology of every tree, chosen for the pose the scene was created at.  For the
+ * reference-form TLAS and the BLASes that topology is the reference's semantics (refitTLAS: it
+ * decides tie order and which exact boxes are tested) and stays.  The flattened instance tree that
+ * renders and ray queries of transformed scenes walk by default (option fit) is a superset filter
+ * only (myraytracer_amd/csrc/wide.h): any topology that holds every (instance, leaf run) pair once
+ * gives the reference's hits, frames and ray counts bit for bit.  Its quality falls as instances
+ * travel; rt_scene_commit_ex with RT_COMMIT_REBUILD_FIT builds it again on the device for the
+ * committed pose (Morton order of the pairs' world boxes, a binary radix tree, collapsed to
+ * four-wide nodes: myraytracer_amd/csrc/rebuild.h).  The caller decides when: there is no automatic
+ * policy.  Measured on C3i: a rebuilding commit costs 4.5 ms against 0.36 ms for a
+ * plain one and 520 to 580 ms for a new rt_scene_create.  A Morton-order tree is worth 0.67 to 0.79
+ * of the host's SAH tree there, so the rebuilt tree renders SLOWER than the refit one while the
+ * instances have moved by up to four of their own diameters (0.86 to 0.88 of it); a rebuild pays
+ * from somewhere between four and eight diameters (1.20 times at eight, 2.27 times at sixteen).
+ *   rt_scene_commit_ex   rt_scene_commit with flags (rt_scene_commit == flags 0).  Staged transforms
+ *       and positions are validated and applied exactly as by rt_scene_commit - a refused commit
+ *       rebuilds nothing and leaves the last rebuild's stats as they were - then the tree is rebuilt
+ *       from the new pose on every replica; with nothing staged a rebuild still rebuilds.  A later
+ *       plain commit refits the new topology.  RT_ERR_UNSUPPORTED without RT_SCENE_DYNAMIC,
+ *       RT_ERR_BUSY as rt_scene_commit, RT_ERR_INVALID_ARG for unknown flag bits.
+ *       Nothing to rebuild is no error: RT_OK with rebuilt = 0 and a reason when the scene has no such
+ *       tree (spheres or planes, motion blur, fewer than two pairs), when the tree is blocked by an
+ *       instance whose transform exceeds the conditioning bound, when the new tree would be deeper
+ *       than the traversal stack allows (or than the test hook rebuild_depth_cap), when its node
+ *       array would reach 4 GB, or when a device allocation fails.  The old tree then stays in place,
+ *       refit as by a plain commit.
+ *   rt_scene_last_rebuild_stats   what the last successful commit did for a rebuild (zeros when it
+ *       asked for none).  rt_commit_stats.total_ms includes the rebuild.
+ * Not rebuilt: the reference-form TLAS, the BLASes, the TLAS's four-wide marker tree (option fit = 0).
+ * Instances can still not be added or removed. */
+#define RT_COMMIT_REBUILD_FIT 1u
+#define RT_REBUILD_NONE        0    /* rt_rebuild_stats.reason: rebuilt, or no rebuild asked for */
+#define RT_REBUILD_NO_TREE     1
+#define RT_REBUILD_BLOCKED     2
+#define RT_REBUILD_TOO_DEEP    3
+#define RT_REBUILD_TOO_LARGE   4
+#define RT_REBUILD_NO_MEMORY   5
+typedef struct rt_rebuild_stats {
+    int32_t rebuilt;            /* 1: the new tree is in use                               */
+    int32_t reason;             /* RT_REBUILD_*: why the old tree stayed                   */
+    int64_t pairs;              /* (instance, leaf run) pairs of the tree                  */
+    int64_t nodes_before, nodes_after;   /* four-wide nodes per octant copy                */
+    int64_t depth_before, depth_after;   /* levels                                         */
+    double  sort_ms;            /* pair boxes, Morton codes, radix sort                    */
+    double  build_ms;           /* hierarchy, node boxes, collapse, octant copies, swap    */
+    double  total_ms;
+} rt_rebuild_stats;
+int32_t rt_scene_commit_ex(rt_scene* scene, uint32_t flags, rt_commit_stats* stats /* may be NULL */);
+int32_t rt_scene_last_rebuild_stats(const rt_scene* scene, rt_rebuild_stats* out);
+
 /* Render options: tuning and test switches, each default being the production setting.
  *   wide (1)             conservative FP32 four-wide walk of identity scenes (exact: wide.h)
  *   unified (1)          one-stack TLAS+BLAS walks; 0 = the nested walk of intersectTLAS
@@ -329,6 +384,9 @@ int32_t rt_scene_get_option(const rt_scene* scene, const char* name, int64_t* va
  *   debug_fail_replica (-1)   inject a launch failure on that replica
  *   wide_delta_scale (1000)   the four-wide walk's widening in 1/1000 of the proven bound
  *                             (wide.h); below 1000 exactness is no longer guaranteed
+ *   rebuild_depth_cap (42)    levels a rebuilt flattened instance tree may have (1 .. 42, the cap
+ *                             that follows from the traversal stack; it can only be lowered): lets a
+ *                             small scene exercise the depth guard of RT_COMMIT_REBUILD_FIT
  * Used only by the parity tests that show the exactness proof has teeth. */
 int32_t rt_scene_set_unsafe_option(rt_scene* scene, const char* name, int64_t value);
 

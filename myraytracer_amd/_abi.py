@@ -94,6 +94,22 @@ class rt_deform_stats(C.Structure):
                 ("validate_ms", C.c_double), ("deform_ms", C.c_double), ("blas_refit_ms", C.c_double)]
 
 
+# ---- rebuilding the flattened instance tree (appended under ABI 5: detected by symbol) ----
+RT_COMMIT_REBUILD_FIT = 1        # rt_scene_commit_ex flag
+(RT_REBUILD_NONE, RT_REBUILD_NO_TREE, RT_REBUILD_BLOCKED, RT_REBUILD_TOO_DEEP, RT_REBUILD_TOO_LARGE,
+ RT_REBUILD_NO_MEMORY) = range(6)
+
+
+class rt_rebuild_stats(C.Structure):
+    _fields_ = [("rebuilt", C.c_int32), ("reason", C.c_int32), ("pairs", C.c_int64),
+                ("nodes_before", C.c_int64), ("nodes_after", C.c_int64),
+                ("depth_before", C.c_int64), ("depth_after", C.c_int64),
+                ("sort_ms", C.c_double), ("build_ms", C.c_double), ("total_ms", C.c_double)]
+
+
+REBUILD_SYMBOLS = ["rt_scene_commit_ex", "rt_scene_last_rebuild_stats"]
+
+
 class rt_wide_dump(C.Structure):
     """rt_debug_wide_build / rt_debug_wide_read (rtcore.h): counts and scalars out, capacities in,
     caller-sized buffers."""
@@ -196,6 +212,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_instance_bounds", "rt_scene_commit", "rt_debug_wide_build", "rt_debug_wide_read",
     "rt_scene_mesh_vertex_count", "rt_scene_set_mesh_positions", "rt_scene_last_deform_stats",
     "rt_query_closest", "rt_query_occluded", "rt_query_stats", "rt_debug_query_tables",
+    "rt_scene_commit_ex", "rt_scene_last_rebuild_stats",
 ]
 RT_ABI_VERSION = 5
 
@@ -309,6 +326,11 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.rt_scene_set_mesh_positions.restype = C.c_int32
         lib.rt_scene_last_deform_stats.argtypes = [C.c_void_p, P(rt_deform_stats)]
         lib.rt_scene_last_deform_stats.restype = C.c_int32
+    if hasattr(lib, "rt_scene_commit_ex"):   # fit-tree rebuild (appended under ABI 5: detected by symbol)
+        lib.rt_scene_commit_ex.argtypes = [C.c_void_p, C.c_uint32, P(rt_commit_stats)]
+        lib.rt_scene_commit_ex.restype = C.c_int32
+        lib.rt_scene_last_rebuild_stats.argtypes = [C.c_void_p, P(rt_rebuild_stats)]
+        lib.rt_scene_last_rebuild_stats.restype = C.c_int32
     if hasattr(lib, "rt_query_closest"):   # ray queries (appended under ABI 5: detected by symbol)
         lib.rt_query_closest.argtypes = [C.c_void_p, C.c_int32, C.c_int64, P(rt_ray_batch), P(rt_hit_batch),
                                          P(rt_query_bounds), C.c_uint32, C.c_void_p]

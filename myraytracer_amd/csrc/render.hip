@@ -31,6 +31,7 @@
 #include "device.h"
 #include "layout.h"
 #include "refit.h"
+#include "rebuild.h"
 #include "scene.h"
 #include "deform.h"
 
@@ -1340,6 +1341,7 @@ enum OptId {
     kOptQueue, kOptQueueLevels, kOptHitlog, kOptNodeshade, kOptLevels, kOptTreePpw, kOptFullFlights,
     kOptDeepCapMb, kOptBatches, kOptZerocopy, kOptSubmitEvents, kOptSubmitCounters, kOptSubmitDma,
     kOptDebugFailReplica, kOptWideDeltaScale, kOptNodeLists, kOptTileOrder, kOptFit, kOptQueueTail, kOptQueryBatch,
+    kOptRebuildDepthCap,
     kOptCount
 };
 // `unsafe` options are test hooks: rt_scene_set_option refuses them (RT_ERR_INVALID_ARG); only the
@@ -1375,6 +1377,8 @@ static const OptDef kOptDefs[kOptCount] = {
     {"queue_tail", 2, 0, 15},             // compacted bounce render: levels >= this one in one k_bounce_tail launch (0 = a launch per level;
                                           // C5 one frame 3.49 -> 3.23 ms, pipelined +0.2 %: profiles/r06t_ab_c5_tail.txt, r06u_ab_c5_tail.txt)
     {"query_batch", 1 << 22, 64, 1 << 30},  // ray queries: rays per launch (and per staging pass of a host-array query)
+    {"rebuild_depth_cap", (kStackCap - 2) / 3, 1, (kStackCap - 2) / 3, true},   // test hook: levels a rebuilt fit tree may have
+                                                                                // (rebuild_fit's depth guard on a small scene)
 };
 
 struct rt_scene {
@@ -1406,6 +1410,7 @@ struct rt_scene {
     };
     std::vector<StagedDeform> staged_deform;
     rt_deform_stats last_deform{};
+    rt_rebuild_stats last_rebuild{};                  // of the last successful commit (rt_scene_commit_ex)
 };
 
 static int64_t full_scratch_bytes(const FullScratch& f) {
@@ -2682,9 +2687,246 @@ static bool grow_plain(double** p, int64_t& cap, int64_t need) {
     return true;
 }
 
-int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
+// ---- the flattened instance tree rebuilt for the committed pose (rtcore.h RT_COMMIT_REBUILD_FIT;
+// rebuild.h).  Every replica builds the new tree beside the old one on its own
+// stream; only when all of them hold a valid tree are the node arrays swapped, so a guard that
+// trips (depth, the 4 GB offset limit, an allocation) leaves every replica with the old tree.
+namespace {
+struct DevBuf {                                   // scratch of one rebuild: freed on every path
+    char* base = nullptr;
+    ~DevBuf() { (void)hipFree(base); }
+};
+struct RebuiltTree {                              // what one replica built
+    W4Node* wnodes = nullptr;                     // eight copies of main nodes + new fit nodes
+    int32_t* levels = nullptr;                    // the new fit_levels list on the device
+    std::vector<int64_t> level_count;             // nodes per level, root first
+    int64_t nodes = 0;
+    int32_t reason = RT_REBUILD_NONE;
+    double sort_ms = 0.0, build_ms = 0.0;
+    void drop() { (void)hipFree(wnodes); (void)hipFree(levels); wnodes = nullptr; levels = nullptr; }
+};
+}  // namespace
+
+static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t depth_cap, RebuiltTree& R) {
+    HIP_TRY(hipSetDevice(r.device));
+    const auto t0 = std::chrono::steady_clock::now();
+    auto ms_since = [](std::chrono::steady_clock::time_point t) {
+        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
+    };
+    const int64_t n = (int64_t)S.fpairs.size(), n_main = S.fit_root, old_copy = S.wide_copy;
+    const int64_t B = dev::kRbBlock;
+    auto grid = [&](int64_t items) { return dim3((unsigned)std::max<int64_t>(1, (items + B - 1) / B)); };
+    hipStream_t st = r.stream;
+    size_t sort_bytes = 0, scan_bytes = 0;
+    {
+        unsigned long long* k = nullptr;
+        uint32_t* v = nullptr;
+        int32_t* c = nullptr;
+        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, k, v, v, (int)n, 0, 63, st));
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, c, c, (int)n, st));
+    }
+    const int parts = (int)std::min<int64_t>(dev::kRbParts, (n + B - 1) / B);
+    // one allocation, carved into 256-byte aligned parts: n pairs, n - 1 binary nodes, at most
+    // n - 1 four-wide nodes (each takes the subtree of a binary node of its own)
+    size_t total = 0;
+    auto take = [&](int64_t count, size_t elem) {
+        const size_t at = total;
+        total += ((size_t)std::max<int64_t>(count, 1) * elem + 255) & ~size_t(255);
+        return at;
+    };
+    const size_t o_pbox = take(6 * n, 8), o_partial = take(6 * (int64_t)parts, 8), o_ubox = take(6, 8), o_nbox = take(6 * n, 8),
+                 o_keys0 = take(n, 8), o_keys1 = take(n, 8), o_vals0 = take(n, 4), o_vals1 = take(n, 4), o_arrive = take(n, 4),
+                 o_left = take(n, 4), o_right = take(n, 4), o_parent = take(n, 4), o_leaf_parent = take(n, 4),
+                 o_cur = take(n, 4), o_next = take(n, 4), o_slots = take(4 * n, 4), o_cnt = take(n + 1, 4),
+                 o_off = take(n + 1, 4), o_wn = take(n, sizeof(W4Node)), o_sort = take((int64_t)sort_bytes, 1),
+                 o_scan = take((int64_t)scan_bytes, 1);
+    DevBuf buf;
+    if (hipMalloc((void**)&buf.base, total) != hipSuccess) {
+        (void)hipGetLastError();
+        buf.base = nullptr;
+        R.reason = RT_REBUILD_NO_MEMORY;
+        return RT_OK;
+    }
+    char* const m = buf.base;
+    double *pbox = (double*)(m + o_pbox), *partial = (double*)(m + o_partial), *ubox = (double*)(m + o_ubox),
+           *nbox = (double*)(m + o_nbox);
+    unsigned long long *keys0 = (unsigned long long*)(m + o_keys0), *keys1 = (unsigned long long*)(m + o_keys1);
+    uint32_t *vals0 = (uint32_t*)(m + o_vals0), *vals1 = (uint32_t*)(m + o_vals1);
+    unsigned* arrive = (unsigned*)(m + o_arrive);
+    int32_t *left = (int32_t*)(m + o_left), *right = (int32_t*)(m + o_right), *parent = (int32_t*)(m + o_parent),
+            *leaf_parent = (int32_t*)(m + o_leaf_parent), *cur = (int32_t*)(m + o_cur), *next = (int32_t*)(m + o_next),
+            *slots = (int32_t*)(m + o_slots), *cnt = (int32_t*)(m + o_cnt), *off = (int32_t*)(m + o_off);
+    W4Node* wn = (W4Node*)(m + o_wn);
+    void *sort_tmp = m + o_sort, *scan_tmp = m + o_scan;
+    // 1. pair boxes and their union, Morton codes, the stable sort
+    hipLaunchKernelGGL(dev::k_rb_pair_boxes, dim3((unsigned)parts), dim3(dev::kRbBlock), 0, st, (const DFitPair*)r.fpairs,
+                       (const double*)r.lbox, (const DInstance*)r.insts, n, pbox, partial);
+    hipLaunchKernelGGL(dev::k_rb_union, dim3(1), dim3(64), 0, st, (const double*)partial, parts, ubox);
+    hipLaunchKernelGGL(dev::k_rb_morton, grid(n), dim3(dev::kRbBlock), 0, st, (const double*)pbox, (const double*)ubox, n, keys0,
+                       vals0);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, keys0, keys1, vals0, vals1, (int)n, 0, 63, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    R.sort_ms = ms_since(t0);
+    const auto t1 = std::chrono::steady_clock::now();
+    // 2. the binary radix tree and its boxes
+    dev::RbTree T{};
+    T.keys = keys1; T.n = (int32_t)n; T.left = left; T.right = right; T.parent = parent; T.leaf_parent = leaf_parent;
+    HIP_TRY(hipMemsetAsync(arrive, 0, (size_t)n * sizeof(unsigned), st));
+    hipLaunchKernelGGL(dev::k_rb_hierarchy, grid(n - 1), dim3(dev::kRbBlock), 0, st, T);
+    hipLaunchKernelGGL(dev::k_rb_node_boxes, grid(n), dim3(dev::kRbBlock), 0, st, T, (const uint32_t*)vals1, (const double*)pbox,
+                       arrive, nbox);
+    HIP_TRY(hipGetLastError());
+    // 3. four-wide nodes, a level per pass: the level's nodes are wn[base, base + count)
+    HIP_TRY(hipMemsetAsync(cur, 0, sizeof(int32_t), st));                   // the root: binary node 0
+    int64_t base = 0, count = 1;
+    for (;;) {
+        if ((int64_t)R.level_count.size() + 1 > depth_cap) { R.reason = RT_REBUILD_TOO_DEEP; return RT_OK; }
+        if (8 * (size_t)(n_main + base + count) * sizeof(W4Node) >= (size_t(1) << 32)) { R.reason = RT_REBUILD_TOO_LARGE; return RT_OK; }
+        if (base + count > n - 1) return fail(RT_ERR_DEVICE, "rebuild: more four-wide nodes than binary nodes");
+        dev::RbLevel L{};
+        L.left = left; L.right = right; L.nbox = nbox; L.pbox = pbox; L.sorted = vals1; L.cur = cur; L.count = (int32_t)count;
+        L.slots = slots; L.cnt = cnt; L.off = off; L.next = next; L.nodes = wn + base;
+        L.child_base = (int32_t)(n_main + base + count);
+        hipLaunchKernelGGL(dev::k_rb_collapse, grid(count + 1), dim3(dev::kRbBlock), 0, st, L);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, cnt, off, (int)(count + 1), st));
+        hipLaunchKernelGGL(dev::k_rb_emit, grid(4 * count), dim3(dev::kRbBlock), 0, st, L);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        int32_t total = 0;
+        HIP_TRY(hipMemcpy(&total, off + count, sizeof(total), hipMemcpyDeviceToHost));
+        R.level_count.push_back(count);
+        base += count;
+        if (total <= 0) break;
+        count = total;
+        std::swap(cur, next);
+    }
+    R.nodes = base;
+    // 4. the new node array: the eight main parts as they are, the new fit nodes behind copy 0's,
+    //    then their octant copies (refit.h k_octant_copies over the level list, deepest level first)
+    const int64_t new_copy = n_main + R.nodes;
+    if (hipMalloc((void**)&R.wnodes, (size_t)(8 * new_copy) * sizeof(W4Node)) != hipSuccess ||
+        hipMalloc((void**)&R.levels, (size_t)R.nodes * sizeof(int32_t)) != hipSuccess) {
+        (void)hipGetLastError();
+        R.drop();
+        R.reason = RT_REBUILD_NO_MEMORY;
+        return RT_OK;
+    }
+    for (int o = 0; o < 8 && n_main > 0; ++o)
+        HIP_TRY(hipMemcpyAsync(R.wnodes + (size_t)o * new_copy, r.wnodes + (size_t)o * old_copy, (size_t)n_main * sizeof(W4Node),
+                               hipMemcpyDeviceToDevice, st));
+    HIP_TRY(hipMemcpyAsync(R.wnodes + n_main, wn, (size_t)R.nodes * sizeof(W4Node), hipMemcpyDeviceToDevice, st));
+    std::vector<int32_t> list;
+    list.reserve((size_t)R.nodes);
+    {
+        int64_t end = n_main + R.nodes;
+        for (size_t l = R.level_count.size(); l-- > 0;) {
+            const int64_t first = end - R.level_count[l];
+            for (int64_t k = first; k < end; ++k) list.push_back((int32_t)k);
+            end = first;
+        }
+    }
+    HIP_TRY(hipMemcpyAsync(R.levels, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(dev::k_octant_copies, grid(R.nodes), dim3(256), 0, st, R.wnodes, (const int32_t*)R.levels, R.nodes, new_copy);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    R.build_ms = ms_since(t1);
+    return RT_OK;
+}
+
+// The rebuild step of a commit (the scene lock is held, no render is in flight).  Returns RT_OK
+// also when nothing was rebuilt (s->last_rebuild says why); an error only for a device failure.
+static int32_t rebuild_fit(rt_scene* s) {
+    const auto t0 = std::chrono::steady_clock::now();
+    HostScene& S = s->host;
+    rt_rebuild_stats st{};
+    const bool has = S.fit_root >= 0 && S.wide_copy > 0 && !S.winst.empty();
+    st.pairs = has ? (int64_t)S.fpairs.size() : 0;
+    st.nodes_before = st.nodes_after = has ? S.fit_nodes : 0;
+    st.depth_before = st.depth_after = has ? S.fit_depth : 0;
+    auto done = [&](int32_t reason) {
+        st.reason = reason;
+        st.rebuilt = reason == RT_REBUILD_NONE ? 1 : 0;
+        st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        s->last_rebuild = st;
+        return (int32_t)RT_OK;
+    };
+    bool tree = has && S.fpairs.size() >= 2 && S.fpairs.size() < (size_t(1) << 30);
+    for (const DeviceReplica& r : s->devs) tree = tree && r.wnodes && r.fpairs && r.lbox && r.insts;
+    if (!tree) return done(RT_REBUILD_NO_TREE);
+    if (S.dyn.fit_blocked) return done(RT_REBUILD_BLOCKED);
+    try {
+        std::vector<RebuiltTree> res(s->devs.size());
+        auto drop_all = [&]() {
+            for (size_t k = 0; k < res.size(); ++k) {
+                (void)hipSetDevice(s->devs[k].device);
+                res[k].drop();
+            }
+        };
+        for (size_t k = 0; k < res.size(); ++k) {
+            const int32_t rc = rebuild_fit_on(S, s->devs[k], s->opt[kOptRebuildDepthCap], res[k]);
+            if (rc == RT_OK && res[k].reason == RT_REBUILD_NONE && res[k].level_count == res[0].level_count) continue;
+            const int32_t reason = res[k].reason;
+            drop_all();
+            if (rc != RT_OK) return rc;
+            if (reason != RT_REBUILD_NONE) return done(reason);
+            return fail(RT_ERR_DEVICE, "rebuild: the replicas built different trees");
+        }
+        for (size_t k = 0; k < res.size(); ++k) {
+            DeviceReplica& r = s->devs[k];
+            HIP_TRY(hipSetDevice(r.device));
+            (void)hipFree(r.wnodes);                        // no kernel holds it: commits do not run beside renders
+            (void)hipFree(r.fit_levels);
+            r.wnodes = res[k].wnodes;
+            r.fit_levels = res[k].levels;
+            r.bytes += (8 * (res[k].nodes - S.fit_nodes)) * (int64_t)sizeof(W4Node) +
+                       (res[k].nodes - (int64_t)std::max<size_t>(1, S.dyn.fit_levels.nodes.size())) * (int64_t)sizeof(int32_t);
+            st.sort_ms = std::max(st.sort_ms, res[k].sort_ms);
+            st.build_ms = std::max(st.build_ms, res[k].build_ms);
+        }
+        // what the host keeps: the counts renders and queries are made from, and the level lists
+        // a later plain commit refits
+        const RebuiltTree& R0 = res[0];
+        RefitLevels& L = S.dyn.fit_levels;
+        L.nodes.clear(); L.off.clear();
+        int64_t end = S.fit_root + R0.nodes;
+        for (size_t l = R0.level_count.size(); l-- > 0;) {
+            L.off.push_back((int64_t)L.nodes.size());
+            for (int64_t k = end - R0.level_count[l]; k < end; ++k) L.nodes.push_back((int32_t)k);
+            end -= R0.level_count[l];
+        }
+        L.off.push_back((int64_t)L.nodes.size());
+        S.wide_copy = S.fit_root + R0.nodes;
+        S.fit_nodes = R0.nodes;
+        S.fit_depth = (int64_t)R0.level_count.size();
+        st.nodes_after = S.fit_nodes;
+        st.depth_after = S.fit_depth;
+        return done(RT_REBUILD_NONE);
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    }
+}
+
+static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats);
+
+int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) { return commit_impl(s, 0u, stats); }
+
+int32_t rt_scene_commit_ex(rt_scene* s, uint32_t flags, rt_commit_stats* stats) { return commit_impl(s, flags, stats); }
+
+int32_t rt_scene_last_rebuild_stats(const rt_scene* s, rt_rebuild_stats* out) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
+    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
+    *out = s->last_rebuild;
+    return RT_OK;
+}
+
+static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) {
     if (stats) *stats = rt_commit_stats{};
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (flags & ~RT_COMMIT_REBUILD_FIT) return fail(RT_ERR_INVALID_ARG, "unknown commit flags");
+    const bool rebuild = (flags & RT_COMMIT_REBUILD_FIT) != 0;
     if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
     std::lock_guard<std::mutex> lock(s->mu);
     if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
@@ -2694,8 +2936,15 @@ int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
     };
     s->last_deform = rt_deform_stats{};
     if (s->staged.empty() && s->staged_deform.empty()) {
+        int32_t rc = RT_OK;
+        if (rebuild) {                                       // nothing staged: the pose as it stands
+            rc = rebuild_fit(s);
+            if (rc == RT_OK) drop_tile_orders(s);
+        } else {
+            s->last_rebuild = rt_rebuild_stats{};
+        }
         if (stats) stats->total_ms = ms_since(t0);
-        return RT_OK;
+        return rc;
     }
     try {
         HostScene& S = s->host;
@@ -2987,10 +3236,17 @@ int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) {
         }
         drop_tile_orders(s);
         s->last_deform = dst;
+        const double refit_ms = ms_since(t1);
+        // 5. on request the flattened instance tree again, from the pose just committed
+        if (rebuild) {
+            if ((rc = rebuild_fit(s)) != RT_OK) return rc;
+        } else {
+            s->last_rebuild = rt_rebuild_stats{};
+        }
         if (stats) {
             stats->instances_moved = (int64_t)n;
             stats->bounds_ms = bounds_ms;
-            stats->refit_ms = ms_since(t1);
+            stats->refit_ms = refit_ms;
             stats->total_ms = ms_since(t0);
         }
         return RT_OK;

@@ -260,7 +260,9 @@ struct TwParked {
 // <= bcoord, so its world image and the products nl * lc stay below the bound - and a larger R
 // only loosens the filter.  An instance whose transform exceeds kFitKappa blocks the fit walk
 // (renders take tw_walk) until a later commit passes; a scene built without this tree never
-// gets one.
+// gets one.  On request (rt_scene_commit_ex, RT_COMMIT_REBUILD_FIT) a commit builds this tree again
+// on the device for the pose just committed (rebuild.h): another topology over the same pairs, with
+// the same slot-box conventions, so the argument above holds for it word for word.
 __device__ __forceinline__ bool fit_boxes_exact(const RenderParams& P, int k, int t0, const V3& o, const V3& d,
                                                 const V3& ol, const V3& dl) {
     const DWideInst& WI = P.winst[k];

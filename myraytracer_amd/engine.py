@@ -210,10 +210,23 @@ class RayTracerEngine:
         _check(load_library().rt_scene_set_camera(self._h, int(index), C.byref(cc)))
         self.scene.cameras[index] = camera
 
-    def commit(self) -> A.rt_commit_stats:
-        """Apply the staged transforms (rt_scene_commit): blocks until every replica is updated."""
+    def commit(self, rebuild: bool = False) -> A.rt_commit_stats:
+        """Apply the staged transforms (rt_scene_commit): blocks until every replica is updated.
+        With `rebuild` the flattened instance tree is then built again on the device for the new
+        pose (rt_scene_commit_ex, RT_COMMIT_REBUILD_FIT); last_rebuild_stats() says what happened."""
         st = A.rt_commit_stats()
-        _check(load_library().rt_scene_commit(self._h, C.byref(st)))
+        lib = load_library()
+        if rebuild:
+            _check(lib.rt_scene_commit_ex(self._h, A.RT_COMMIT_REBUILD_FIT, C.byref(st)))
+        else:
+            _check(lib.rt_scene_commit(self._h, C.byref(st)))
+        return st
+
+    def last_rebuild_stats(self) -> A.rt_rebuild_stats:
+        """What the last commit() did for a rebuild (rt_scene_last_rebuild_stats): zeros when it
+        asked for none; rebuilt = 0 and a reason (RT_REBUILD_*) when the old tree stayed."""
+        st = A.rt_rebuild_stats()
+        _check(load_library().rt_scene_last_rebuild_stats(self._h, C.byref(st)))
         return st
 
     # -- deforming meshes (BVHBuilder.refit applied to a BLAS, BVH.swift:254-291)
