@@ -7,6 +7,7 @@
 """
 from __future__ import annotations
 
+import glob
 import os
 import shutil
 import subprocess
@@ -37,7 +38,7 @@ def _stale(target, sources):
 def build_product(force: bool = False) -> str:
     out = os.path.join(PKG, "libmyrt.so")
     srcs = [os.path.join(CSRC, s) for s in PRODUCT_SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in ("layout.h", "scene.h", "device.h", "wide.h", "render_full.h", "refit.h", "rebuild.h", "deform.h", "query.h")] + [os.path.join(ROOT, "include", "rtcore.h")]
+    deps = srcs + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(ROOT, "include", "rtcore.h")]
     if force or _stale(out, deps):
         _run([HIPCC, "--offload-arch=gfx950", *COMMON_FLAGS, "-o", out, *srcs])
     return out

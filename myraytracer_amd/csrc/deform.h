@@ -5,7 +5,7 @@
 // min / max over its primitives' bounds and an inner node's the union of its children's.
 //
 //   k_deform_validate (+ _final)  one staged position array -> (all finite, largest |coordinate|):
-//       FP64, wave shuffles, one partial per block, a final pass (refit.h k_inst_bounds' scheme).
+//       FP64, wave shuffles, one partial per block, a final pass (refit.h's reduction order).
 //       The whole array is read: a NaN in a vertex no triangle uses is refused too.
 //   k_deform_tris      one thread per TriRec of the BLAS's run: v0, e1 = v1 - v0, e2 = v2 - v0 (the
 //       builder's expressions, scene.cpp "independent per triangle"), the triangle's exact box
@@ -22,9 +22,8 @@
 //       leaf run's box (ref < 0) or the union of record ref[c]'s two child boxes.  Pure min / max.
 //   k_blas_root        the BLAS root box (DInstance::root_lo / root_hi, DWideInst::bcoord) and the
 //       reduced |e1||e2|, read back by the host.
-//   k_refit_blas_level one level of the BLAS's four-wide nodes: a leaf-run slot takes
-//       refit_down / refit_up of lbox[~ref], an inner slot the float union of its child's slots;
-//       refit.h k_octant_copies then restates the eight copies.
+//   The BLAS's four-wide nodes are refit level by level by refit.h k_refit_level<LeafRunBox>, its
+//       eight copies restated by k_octant_copies.
 //
 // Why the hits stay the reference's: the four-wide trees only have to be supersets (wide.h), and a
 // refit tree is one.  A candidate is accepted only after the reference's exact FP64 tests against
@@ -83,10 +82,8 @@ __global__ __launch_bounds__(kDeformBlock) void k_deform_validate(const double* 
         if (!(a < HUGE_VAL)) ok = 0.0;                    // NaN or infinite
         mx = fmax(mx, a);
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        ok = fmin(ok, __shfl_xor(ok, off, 64));
-        mx = fmax(mx, __shfl_xor(mx, off, 64));
-    }
+    ok = wave_fmin(ok);
+    mx = wave_fmax(mx);
     __shared__ double sm[kDeformBlock / 64][2];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0) { sm[wave][0] = ok; sm[wave][1] = mx; }
@@ -100,10 +97,8 @@ __global__ __launch_bounds__(kDeformBlock) void k_deform_validate(const double* 
 __global__ __launch_bounds__(64) void k_deform_validate_final(const double* partial, int parts, double* out) {
     double ok = 1.0, mx = 0.0;
     for (int p = threadIdx.x; p < parts; p += 64) { ok = fmin(ok, partial[2 * p]); mx = fmax(mx, partial[2 * p + 1]); }
-    for (int off = 32; off > 0; off >>= 1) {
-        ok = fmin(ok, __shfl_xor(ok, off, 64));
-        mx = fmax(mx, __shfl_xor(mx, off, 64));
-    }
+    ok = wave_fmin(ok);
+    mx = wave_fmax(mx);
     if (threadIdx.x == 0) { out[0] = ok; out[1] = mx; }
 }
 
@@ -147,7 +142,7 @@ __global__ __launch_bounds__(kDeformBlock) void k_deform_tris(DeformMesh M, TriR
             }
         }
     }
-    for (int off = 32; off > 0; off >>= 1) p = fmax(p, __shfl_xor(p, off, 64));
+    p = wave_fmax(p);
     __shared__ double sm[kDeformBlock / 64];
     if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = p;
     __syncthreads();
@@ -245,32 +240,13 @@ __global__ __launch_bounds__(64) void k_blas_root(const WRec* recs, int32_t root
                                                   double* out) {
     double p = 0.0;
     for (int q = threadIdx.x; q < parts; q += 64) p = fmax(p, ppart[q]);
-    for (int off = 32; off > 0; off >>= 1) p = fmax(p, __shfl_xor(p, off, 64));
+    p = wave_fmax(p);
     if (threadIdx.x != 0) return;
     double lo[3], hi[3];
     rec_child_box(recs, R, root_ref, lo, hi);
     for (int k = 0; k < 3; ++k) { out[k] = lo[k]; out[3 + k] = hi[k]; }
     out[6] = p;
     out[7] = 0.0;
-}
-
-// One thread per slot of the level's four-wide BLAS nodes (octant copy 0)
-__global__ __launch_bounds__(kDeformBlock) void k_refit_blas_level(W4Node* nodes, const int32_t* list, int32_t count,
-                                                                   const double* lbox) {
-    const int64_t i = (int64_t)blockIdx.x * kDeformBlock + threadIdx.x;
-    if (i >= 4 * (int64_t)count) return;
-    W4Node& n = nodes[list[i >> 2]];
-    const int c = (int)(i & 3);
-    if (refit_slot_empty(n, c)) return;
-    const int32_t ref = n.ref[c];
-    float lo[3], hi[3];
-    if (ref >= 0) {                                           // union of the child node's slots
-        refit_slot_union(nodes[ref], lo, hi);
-    } else {                                                  // leaf run: its exact box, rounded outward
-        const double* b = lbox + 6 * (size_t)~ref;
-        for (int k = 0; k < 3; ++k) { lo[k] = refit_down(b[k]); hi[k] = refit_up(b[3 + k]); }
-    }
-    for (int k = 0; k < 3; ++k) { n.pnear[k][c] = lo[k]; n.pfar[k][c] = hi[k]; }
 }
 
 }  // namespace dev

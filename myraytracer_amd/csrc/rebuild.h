@@ -9,9 +9,8 @@
 // created at; this builds one for the pose it has now.  The pair array is not touched: terminal
 // slot ~p still names pair p, and fit_walk / fit_boxes_exact change nowhere.
 //
-//   k_rb_pair_boxes (+ k_rb_union)  every pair's FP64 world box - the eight corners of lbox[pair.t0]
-//       through l2w[pair.inst], min / max, build_fit's and k_refit_level's formula term for term -
-//       and the union of all of them (min / max only: the order of the reduction does not matter).
+//   k_rb_pair_boxes  every pair's FP64 world box (refit.h pair_world_box, which k_refit_level calls
+//       too) and the union of all of them (refit.h block_box_union, then one block of k_fold_boxes).
 //   k_rb_morton     63-bit Morton code, 21 bits per axis, of the pair's centroid normalised by that
 //       union in FP64.  An axis of zero extent gives code bits 0 (no division).  The (code, pair)
 //       records are then sorted by hipcub's stable device radix sort; equal codes keep pair order.
@@ -49,23 +48,6 @@ constexpr int kRbParts = 1024;            // blocks of k_rb_pair_boxes at the mo
 constexpr int kRbMaxClimb = 128;          // a radix tree over 63 + 32 prefix bits is shallower
 constexpr int32_t kRbEmpty = INT32_MIN;   // an empty slot of k_rb_collapse (pairs stay below 2^30)
 
-// The pair's world box: scene.cpp build_fit / refit.h k_refit_level, term for term.
-__device__ __forceinline__ void rb_pair_box(const DFitPair p, const double* lbox, const DInstance* insts, double wlo[3],
-                                            double whi[3]) {
-    const double* x = lbox + 6 * (size_t)p.t0;
-    const double* M = insts[p.inst].l2w;
-    for (int a = 0; a < 3; ++a) { wlo[a] = HUGE_VAL; whi[a] = -HUGE_VAL; }
-    for (int q = 0; q < 8; ++q) {
-        const double px = (q & 1) ? x[3] : x[0], py = (q & 2) ? x[4] : x[1], pz = (q & 4) ? x[5] : x[2];
-#pragma unroll
-        for (int a = 0; a < 3; ++a) {
-            const double v = M[a] * px + M[4 + a] * py + M[8 + a] * pz + M[12 + a];
-            wlo[a] = v < wlo[a] ? v : wlo[a];
-            whi[a] = v > whi[a] ? v : whi[a];
-        }
-    }
-}
-
 // Grid-stride over the pairs: pbox[6 p] and one partial union per block (partial[6 * blockIdx.x]).
 __global__ __launch_bounds__(kRbBlock) void k_rb_pair_boxes(const DFitPair* fpairs, const double* lbox,
                                                             const DInstance* insts, int64_t n, double* pbox,
@@ -74,48 +56,15 @@ __global__ __launch_bounds__(kRbBlock) void k_rb_pair_boxes(const DFitPair* fpai
     const int64_t stride = (int64_t)gridDim.x * kRbBlock;
     for (int64_t p = (int64_t)blockIdx.x * kRbBlock + threadIdx.x; p < n; p += stride) {
         double wlo[3], whi[3];
-        rb_pair_box(fpairs[p], lbox, insts, wlo, whi);
+        pair_world_box(fpairs[p], lbox, insts, wlo, whi);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             pbox[6 * p + k] = wlo[k]; pbox[6 * p + 3 + k] = whi[k];
             lo[k] = fmin(lo[k], wlo[k]); hi[k] = fmax(hi[k], whi[k]);
         }
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[k] = fmin(lo[k], __shfl_xor(lo[k], off, 64));
-            hi[k] = fmax(hi[k], __shfl_xor(hi[k], off, 64));
-        }
-    __shared__ double sm[kRbBlock / 64][6];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0)
-        for (int k = 0; k < 3; ++k) { sm[wave][k] = lo[k]; sm[wave][3 + k] = hi[k]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const bool mn = threadIdx.x < 3;
-        double v = sm[0][threadIdx.x];
-        for (int w = 1; w < kRbBlock / 64; ++w) v = mn ? fmin(v, sm[w][threadIdx.x]) : fmax(v, sm[w][threadIdx.x]);
-        partial[(size_t)blockIdx.x * 6 + threadIdx.x] = v;
-    }
-}
-
-// One wave: `parts` partial unions -> ubox[6]
-__global__ __launch_bounds__(64) void k_rb_union(const double* partial, int parts, double* ubox) {
-    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (int p = threadIdx.x; p < parts; p += 64) {
-        const double* b = partial + (size_t)p * 6;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], b[k]); hi[k] = fmax(hi[k], b[3 + k]); }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[k] = fmin(lo[k], __shfl_xor(lo[k], off, 64));
-            hi[k] = fmax(hi[k], __shfl_xor(hi[k], off, 64));
-        }
-    if (threadIdx.x == 0)
-        for (int k = 0; k < 3; ++k) { ubox[k] = lo[k]; ubox[3 + k] = hi[k]; }
+    const double v = block_box_union<kRbBlock>(lo, hi);
+    if (threadIdx.x < 6) partial[(size_t)blockIdx.x * 6 + threadIdx.x] = v;
 }
 
 // 21 bits -> every third bit of 63

@@ -2,18 +2,19 @@
 // transforms and can only be recomputed where the data lives, because rt_scene_create drops the
 // host's triangles, leaf boxes and four-wide nodes after upload.
 //
-//   k_inst_bounds (+ k_inst_bounds_final)  Instance.worldBounds of every moved triangle-mesh
+//   k_inst_bounds (+ k_fold_boxes)  Instance.worldBounds of every moved triangle-mesh
 //       instance: the union over its BLAS's triangles of AABB.transformed(by: localToWorld) of the
 //       triangle's local box (refitTLAS step 1, RTContext.swift:889-900; scene.cpp
 //       aabb_transformed, restated term for term: the build uses -ffp-contract=off on host and
 //       device, so a box equals the host's bit for bit).  min / max are order-independent, so the
 //       reduction (FP64, wave shuffles, one partial per block, a final pass) gives the host loop's
-//       values; -0 and +0 compare equal and no box test sees the sign of a zero.
+//       values; -0 and +0 compare equal and no box test sees the sign of a zero.  The reductions
+//       (block_box_union, k_fold_boxes) are shared with rebuild.h and deform.h.
 //   k_refit_level  one level of a four-wide tree, bottom-up (a launch per level, deepest first;
-//       scene.h RefitLevels): a terminal slot takes its box again - the TLAS's instance markers
-//       their TLAS leaf box (DWideInst::tbox), the flattened instance tree's pairs the eight corners
-//       of their leaf box through the instance's new localToWorld (scene.cpp build_fit's formula) -
-//       rounded outward to float; an inner slot takes the union of its child node's slots; empty
+//       scene.h RefitLevels): a terminal slot takes its box again, rounded outward to float - by
+//       TreeSlotBox the TLAS's instance markers their TLAS leaf box (DWideInst::tbox) and the
+//       flattened instance tree's pairs pair_world_box; by LeafRunBox a deformed BLAS's leaf runs
+//       their lbox (deform.h) - an inner slot takes the union of its child node's slots; empty
 //       slots stay +inf.  Works on octant copy 0, whose slots are in sorted order: a child is found
 //       by its ref, and a union does not depend on the order.
 //   k_octant_copies  the eight octant copies of the refit nodes again (scene.cpp
@@ -44,6 +45,47 @@ struct RefitMove {            // one moved triangle-mesh instance
     int32_t blur, pad;
 };
 constexpr int kBoundsBlock = 256;
+
+// ---- reductions shared by the commit kernels (refit.h, deform.h, rebuild.h).  The order of the
+// operations is part of what a commit writes (fmin / fmax of -0.0 and +0.0 may depend on it):
+// shuffle-xor offsets 32 down to 1, then a block's waves in order, partials with stride 64.
+__device__ __forceinline__ double wave_fmin(double v) { for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_xor(v, off, 64)); return v; }
+__device__ __forceinline__ double wave_fmax(double v) { for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64)); return v; }
+__device__ __forceinline__ void wave_box_union(double lo[3], double hi[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { lo[k] = wave_fmin(lo[k]); hi[k] = wave_fmax(hi[k]); }
+}
+// The union of the boxes of a block of BLOCK threads (all of them call): thread k < 6 is returned
+// component k of it (lo in 0..2, hi in 3..5) and writes it where the kernel keeps its partials.
+template <int BLOCK>
+__device__ __forceinline__ double block_box_union(double lo[3], double hi[3]) {
+    wave_box_union(lo, hi);
+    __shared__ double sm[BLOCK / 64][6];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (lane == 0)
+        for (int k = 0; k < 3; ++k) { sm[wave][k] = lo[k]; sm[wave][3 + k] = hi[k]; }
+    __syncthreads();
+    double v = 0.0;
+    if (threadIdx.x < 6) {
+        const bool mn = threadIdx.x < 3;
+        v = sm[0][threadIdx.x];
+        for (int w = 1; w < BLOCK / 64; ++w) v = mn ? fmin(v, sm[w][threadIdx.x]) : fmax(v, sm[w][threadIdx.x]);
+    }
+    return v;
+}
+// One wave per block: block b folds the `parts` partial boxes from partial[6 * parts * b] -> out[6 * b]
+// (a moved instance's partials, k_inst_bounds; with one block all of rebuild.h k_rb_pair_boxes')
+__global__ __launch_bounds__(64) void k_fold_boxes(const double* partial, int parts, double* out) {
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (int p = threadIdx.x; p < parts; p += 64) {
+        const double* b = partial + ((size_t)blockIdx.x * parts + p) * 6;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], b[k]); hi[k] = fmax(hi[k], b[3 + k]); }
+    }
+    wave_box_union(lo, hi);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < 3; ++k) { out[6 * (size_t)blockIdx.x + k] = lo[k]; out[6 * (size_t)blockIdx.x + 3 + k] = hi[k]; }
+}
 
 // AABB.transformed(by:) (AABB.swift:71-92) in scene.cpp aabb_transformed's operation order
 __device__ __forceinline__ void refit_aabb_transformed(const double lo[3], const double hi[3], const double* M,
@@ -99,41 +141,8 @@ __global__ __launch_bounds__(kBoundsBlock) void k_inst_bounds(const CTri* ctris,
 #pragma unroll
         for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], wlo[k]); hi[k] = fmax(hi[k], whi[k]); }
     }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[k] = fmin(lo[k], __shfl_xor(lo[k], off, 64));
-            hi[k] = fmax(hi[k], __shfl_xor(hi[k], off, 64));
-        }
-    __shared__ double sm[kBoundsBlock / 64][6];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0)
-        for (int k = 0; k < 3; ++k) { sm[wave][k] = lo[k]; sm[wave][3 + k] = hi[k]; }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const bool mn = threadIdx.x < 3;
-        double v = sm[0][threadIdx.x];
-        for (int w = 1; w < kBoundsBlock / 64; ++w) v = mn ? fmin(v, sm[w][threadIdx.x]) : fmax(v, sm[w][threadIdx.x]);
-        partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = v;
-    }
-}
-
-// One wave per moved instance: its `parts` partials -> out[6 * instance slot]
-__global__ __launch_bounds__(64) void k_inst_bounds_final(const double* partial, int parts, double* out) {
-    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-    for (int p = threadIdx.x; p < parts; p += 64) {
-        const double* b = partial + ((size_t)blockIdx.x * parts + p) * 6;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { lo[k] = fmin(lo[k], b[k]); hi[k] = fmax(hi[k], b[3 + k]); }
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-        for (int off = 32; off > 0; off >>= 1) {
-            lo[k] = fmin(lo[k], __shfl_xor(lo[k], off, 64));
-            hi[k] = fmax(hi[k], __shfl_xor(hi[k], off, 64));
-        }
-    if (threadIdx.x == 0)
-        for (int k = 0; k < 3; ++k) { out[6 * (size_t)blockIdx.x + k] = lo[k]; out[6 * (size_t)blockIdx.x + 3 + k] = hi[k]; }
+    const double v = block_box_union<kBoundsBlock>(lo, hi);
+    if (threadIdx.x < 6) partial[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 6 + threadIdx.x] = v;
 }
 
 // scene.cpp WideBuilder::down / up: the nearest float not above / not below x
@@ -148,19 +157,7 @@ __device__ __forceinline__ float refit_up(double x) {
     return f;
 }
 
-struct RefitTree {
-    W4Node* nodes;            // octant copy 0 of the node array
-    const int32_t* list;      // the level's nodes
-    int32_t count;
-    int32_t marker_base;      // >= 0: the TLAS's tree, terminal slot ~(marker_base + instance); < 0: the fit tree
-    const DWideInst* winst;
-    const DFitPair* fpairs;
-    const double* lbox;
-    const DInstance* insts;
-};
-
 // An empty slot has +inf planes; an inner slot takes the float union of its child node's slots
-// (shared with deform.h k_refit_blas_level)
 __device__ __forceinline__ bool refit_slot_empty(const W4Node& n, int c) { return !(n.pnear[0][c] < HUGE_VALF); }
 __device__ __forceinline__ void refit_slot_union(const W4Node& ch, float lo[3], float hi[3]) {
     for (int k = 0; k < 3; ++k) { lo[k] = HUGE_VALF; hi[k] = -HUGE_VALF; }
@@ -172,34 +169,68 @@ __device__ __forceinline__ void refit_slot_union(const W4Node& ch, float lo[3], 
     }
 }
 
-// One thread per slot of the level's nodes.
-__global__ __launch_bounds__(256) void k_refit_level(RefitTree T) {
+// The world box of an (instance, leaf run) pair of the flattened instance tree: the eight corners
+// of the leaf box through the instance's localToWorld, min / max (scene.cpp build_fit's formula,
+// term for term)
+__device__ __forceinline__ void pair_world_box(const DFitPair p, const double* lbox, const DInstance* insts, double wlo[3],
+                                               double whi[3]) {
+    const double* x = lbox + 6 * (size_t)p.t0;
+    const double* M = insts[p.inst].l2w;
+    for (int a = 0; a < 3; ++a) { wlo[a] = HUGE_VAL; whi[a] = -HUGE_VAL; }
+    for (int q = 0; q < 8; ++q) {
+        const double px = (q & 1) ? x[3] : x[0], py = (q & 2) ? x[4] : x[1], pz = (q & 4) ? x[5] : x[2];
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            const double v = M[a] * px + M[4 + a] * py + M[8 + a] * pz + M[12 + a];
+            wlo[a] = v < wlo[a] ? v : wlo[a];
+            whi[a] = v > whi[a] ? v : whi[a];
+        }
+    }
+}
+
+// What a terminal slot (ref < 0) of a refit tree takes its FP64 box from.  TreeSlotBox: the TLAS's
+// tree (marker_base >= 0: slot ~(marker_base + instance), its TLAS leaf's box) or the flattened
+// instance tree (marker_base < 0: slot ~pair).  LeafRunBox (a BLAS's nodes, deform.h): the leaf
+// run's exact box lbox[~ref].
+struct TreeSlotBox {
+    int32_t marker_base;
+    const DWideInst* winst;
+    const DFitPair* fpairs;
+    const double* lbox;
+    const DInstance* insts;
+    __device__ __forceinline__ void operator()(int32_t ref, double lo[3], double hi[3]) const {
+        if (marker_base >= 0) {
+            const double* b = winst[~ref - marker_base].tbox;
+            for (int k = 0; k < 3; ++k) { lo[k] = b[k]; hi[k] = b[3 + k]; }
+        } else {
+            pair_world_box(fpairs[~ref], lbox, insts, lo, hi);
+        }
+    }
+};
+struct LeafRunBox {
+    const double* lbox;
+    __device__ __forceinline__ void operator()(int32_t ref, double lo[3], double hi[3]) const {
+        const double* b = lbox + 6 * (size_t)~ref;
+        for (int k = 0; k < 3; ++k) { lo[k] = b[k]; hi[k] = b[3 + k]; }
+    }
+};
+
+// One thread per slot of the level's `count` nodes list[0 .. count) (octant copy 0): an inner slot
+// takes the union of its child node's slots, a terminal slot its box rounded outward to float.
+template <class TerminalBox>
+__global__ __launch_bounds__(256) void k_refit_level(W4Node* nodes, const int32_t* list, int32_t count, TerminalBox terminal) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= 4 * (int64_t)T.count) return;
-    W4Node& n = T.nodes[T.list[i >> 2]];
+    if (i >= 4 * (int64_t)count) return;
+    W4Node& n = nodes[list[i >> 2]];
     const int c = (int)(i & 3);
     if (refit_slot_empty(n, c)) return;
     const int32_t ref = n.ref[c];
     float lo[3], hi[3];
-    if (ref >= 0) {                                           // union of the child node's slots
-        refit_slot_union(T.nodes[ref], lo, hi);
-    } else if (T.marker_base >= 0) {                          // instance marker: its TLAS leaf's box
-        const double* b = T.winst[~ref - T.marker_base].tbox;
-        for (int k = 0; k < 3; ++k) { lo[k] = refit_down(b[k]); hi[k] = refit_up(b[3 + k]); }
-    } else {                                                  // pair: the leaf box's corners through l2w
-        const DFitPair p = T.fpairs[~ref];
-        const double* x = T.lbox + 6 * (size_t)p.t0;
-        const double* M = T.insts[p.inst].l2w;
-        double wlo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, whi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
-        for (int q = 0; q < 8; ++q) {
-            const double px = (q & 1) ? x[3] : x[0], py = (q & 2) ? x[4] : x[1], pz = (q & 4) ? x[5] : x[2];
-#pragma unroll
-            for (int a = 0; a < 3; ++a) {
-                const double v = M[a] * px + M[4 + a] * py + M[8 + a] * pz + M[12 + a];
-                wlo[a] = v < wlo[a] ? v : wlo[a];
-                whi[a] = v > whi[a] ? v : whi[a];
-            }
-        }
+    if (ref >= 0) {
+        refit_slot_union(nodes[ref], lo, hi);
+    } else {
+        double wlo[3], whi[3];
+        terminal(ref, wlo, whi);
         for (int k = 0; k < 3; ++k) { lo[k] = refit_down(wlo[k]); hi[k] = refit_up(whi[k]); }
     }
     for (int k = 0; k < 3; ++k) { n.pnear[k][c] = lo[k]; n.pfar[k][c] = hi[k]; }

@@ -1251,6 +1251,24 @@ struct TileOrder {
     int64_t used = 0;                         // last use (eviction)
 };
 
+// Commit scratch (commit.h): touched by no render (commits never run beside renders), so it is replaced
+// outright when it has to grow - no 1.5x growth, no retire list - and scratch_bytes does not count it.
+template <class T>
+struct DevArray {
+    T* p = nullptr;
+    int64_t cap = 0;                          // elements
+    bool grow(int64_t need) {
+        if (need <= cap && p) return true;
+        release();
+        need = std::max<int64_t>(need, 1);
+        if (hipMalloc((void**)&p, (size_t)need * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
+        cap = need;
+        return true;
+    }
+    void release() { (void)hipFree(p); p = nullptr; cap = 0; }
+    operator T*() const { return p; }
+};
+
 struct DeviceReplica {
     int device = 0;
     WRec* recs = nullptr;
@@ -1304,8 +1322,8 @@ struct DeviceReplica {
     double* pbox = nullptr;
     int32_t* tlas_levels = nullptr;
     int32_t* fit_levels = nullptr;
-    dev::RefitMove* moves = nullptr; double* bounds_part = nullptr; double* bounds_out = nullptr;
-    int64_t moves_cap = 0, bounds_part_cap = 0;
+    DevArray<dev::RefitMove> moves;
+    DevArray<double> bounds_part, bounds_out;
     // deformable scenes (deform.h): per TriRec its vertex ids, the BLAS records and four-wide nodes by
     // level, the vertex adjacency of derived smooth normals; and scratch grown by a commit: the staged
     // host arrays' device copies, unit face normals and vertex normals of one mesh, the reductions
@@ -1314,11 +1332,7 @@ struct DeviceReplica {
     int32_t* wide_list = nullptr;
     int32_t* csr_off = nullptr;
     int32_t* csr_tri = nullptr;
-    double* def_stage = nullptr; int64_t def_stage_cap = 0;
-    double* def_face = nullptr; int64_t def_face_cap = 0;
-    double* def_vnorm = nullptr; int64_t def_vnorm_cap = 0;
-    double* def_part = nullptr; int64_t def_part_cap = 0;
-    double* def_out = nullptr; int64_t def_out_cap = 0;
+    DevArray<double> def_stage, def_face, def_vnorm, def_part, def_out;
     // ray queries (query.h; rt_query_closest / rt_query_occluded): the staging of host-array
     // queries (grown x1.5, the predecessor retired), the slot's query words on the device and
     // their pinned copy (the three maxima come back through it), the face table (uploaded by the
@@ -1499,10 +1513,9 @@ static void free_replica(DeviceReplica& r) {
     (void)hipFree(r.alights); (void)hipFree(r.jitter); (void)hipFree(r.wave_times);
     (void)hipFree(r.deep);
     (void)hipFree(r.pbox); (void)hipFree(r.tlas_levels); (void)hipFree(r.fit_levels);
-    (void)hipFree(r.moves); (void)hipFree(r.bounds_part); (void)hipFree(r.bounds_out);
+    r.moves.release(); r.bounds_part.release(); r.bounds_out.release();
     (void)hipFree(r.vid); (void)hipFree(r.rec_list); (void)hipFree(r.wide_list); (void)hipFree(r.csr_off); (void)hipFree(r.csr_tri);
-    (void)hipFree(r.def_stage); (void)hipFree(r.def_face); (void)hipFree(r.def_vnorm); (void)hipFree(r.def_part);
-    (void)hipFree(r.def_out);
+    r.def_stage.release(); r.def_face.release(); r.def_vnorm.release(); r.def_part.release(); r.def_out.release();
     (void)hipFree(r.q_buf); (void)hipFree(r.q_words); (void)hipFree(r.q_face); (void)hipFree(r.q_inst_obj);
     if (r.q_host) (void)hipHostFree(r.q_host);
     r.full.release();
@@ -2494,30 +2507,6 @@ static void drop_tile_orders(rt_scene* s) {
     }
 }
 
-int32_t rt_scene_instance_of_object(const rt_scene* s, int32_t object_index, int32_t* instance) {
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (!instance) return fail(RT_ERR_INVALID_ARG, "instance is NULL");
-    if (object_index < 0 || object_index >= (int32_t)s->host.object_inst.size())
-        return fail(RT_ERR_INVALID_ARG, "bad object index");
-    *instance = s->host.object_inst[(size_t)object_index];
-    return RT_OK;
-}
-
-int32_t rt_scene_set_instance_transform(rt_scene* s, int32_t instance, const double m[16]) {
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
-    if (instance < 0 || instance >= (int32_t)s->host.insts.size()) return fail(RT_ERR_INVALID_ARG, "bad instance index");
-    if (!m || !matrix_ok(m))
-        return fail(RT_ERR_INVALID_ARG, "localToWorld must be finite with a non-zero, finite upper 3x3 determinant");
-    std::array<double, 16> a;
-    std::memcpy(a.data(), m, sizeof(double) * 16);
-    std::lock_guard<std::mutex> lock(s->mu);
-    for (auto& e : s->staged)
-        if (e.first == instance) { e.second = a; return RT_OK; }
-    s->staged.push_back({instance, a});
-    return RT_OK;
-}
-
 int32_t rt_scene_set_camera(rt_scene* s, int32_t camera_index, const rt_camera* cam) {
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
     if (!cam) return fail(RT_ERR_INVALID_ARG, "camera is NULL");
@@ -2530,732 +2519,12 @@ int32_t rt_scene_set_camera(rt_scene* s, int32_t camera_index, const rt_camera* 
     return RT_OK;
 }
 
-int32_t rt_scene_instance_bounds(const rt_scene* s, int32_t instance, double lo[3], double hi[3]) {
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (!lo || !hi) return fail(RT_ERR_INVALID_ARG, "NULL argument");
-    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
-    if (instance < 0 || 6 * (size_t)instance + 6 > s->host.inst_bounds.size())
-        return fail(RT_ERR_INVALID_ARG, "bad instance index");
-    const double* b = &s->host.inst_bounds[6 * (size_t)instance];
-    for (int k = 0; k < 3; ++k) { lo[k] = b[k]; hi[k] = b[3 + k]; }
-    return RT_OK;
-}
+}  // extern "C"
 
-// World bounds of the moved triangle-mesh instances, on replica 0 (refit.h k_inst_bounds)
-static int32_t device_instance_bounds(rt_scene* s, const std::vector<dev::RefitMove>& moves, std::vector<double>& out) {
-    DeviceReplica& r = s->devs[0];
-    const HostScene& S = s->host;
-    const int64_t n = (int64_t)moves.size();
-    out.assign(6 * (size_t)n, 0.0);
-    if (n == 0) return RT_OK;
-    HIP_TRY(hipSetDevice(r.device));
-    int64_t most = 1;
-    for (const dev::RefitMove& m : moves) most = std::max<int64_t>(most, m.tri_end - m.tri_first);
-    const int parts = (int)std::min<int64_t>(64, (most + dev::kBoundsBlock * 8 - 1) / (dev::kBoundsBlock * 8));
-    if (r.moves_cap < n) {
-        (void)hipFree(r.moves); (void)hipFree(r.bounds_out);
-        r.moves = nullptr; r.bounds_out = nullptr; r.moves_cap = 0;
-        HIP_TRY(hipMalloc((void**)&r.moves, (size_t)n * sizeof(dev::RefitMove)));
-        HIP_TRY(hipMalloc((void**)&r.bounds_out, (size_t)n * 6 * sizeof(double)));
-        r.moves_cap = n;
-    }
-    if (r.bounds_part_cap < n * parts) {
-        (void)hipFree(r.bounds_part);
-        r.bounds_part = nullptr; r.bounds_part_cap = 0;
-        HIP_TRY(hipMalloc((void**)&r.bounds_part, (size_t)(n * parts) * 6 * sizeof(double)));
-        r.bounds_part_cap = n * parts;
-    }
-    HIP_TRY(hipMemcpy(r.moves, moves.data(), (size_t)n * sizeof(dev::RefitMove), hipMemcpyHostToDevice));
-    const CTri* ct = S.compact_tris ? r.ctris : nullptr;
-    if (!ct && !r.pbox) return fail(RT_ERR_DEVICE, "dynamic scene without triangle boxes");
-    constexpr int64_t kBatch = 32768;                       // gridDim.y
-    for (int64_t b = 0; b < n; b += kBatch) {
-        const int64_t nb = std::min(kBatch, n - b);
-        hipLaunchKernelGGL(dev::k_inst_bounds, dim3((unsigned)parts, (unsigned)nb), dim3(dev::kBoundsBlock), 0, r.stream, ct,
-                           r.pbox, r.moves + b, r.bounds_part + (size_t)b * parts * 6);
-    }
-    hipLaunchKernelGGL(dev::k_inst_bounds_final, dim3((unsigned)n), dim3(64), 0, r.stream, r.bounds_part, parts,
-                       r.bounds_out);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(r.stream));
-    HIP_TRY(hipMemcpy(out.data(), r.bounds_out, (size_t)n * 6 * sizeof(double), hipMemcpyDeviceToHost));
-    return RT_OK;
-}
+// rt_scene_commit and what stages for it: the host side of refit.h, deform.h and rebuild.h
+#include "commit.h"
 
-// One four-wide tree of a replica brought up to date: a launch per level, deepest first, then the
-// eight octant copies of its nodes (refit.h)
-static void refit_tree(const HostScene& S, DeviceReplica& r, const RefitLevels& L, const int32_t* list, int32_t marker_base) {
-    if (L.nodes.empty() || !list) return;
-    dev::RefitTree T{};
-    T.nodes = r.wnodes; T.marker_base = marker_base; T.winst = r.winst; T.fpairs = r.fpairs; T.lbox = r.lbox;
-    T.insts = r.insts;
-    for (size_t l = 0; l + 1 < L.off.size(); ++l) {
-        T.list = list + L.off[l];
-        T.count = (int32_t)(L.off[l + 1] - L.off[l]);
-        if (T.count <= 0) continue;
-        hipLaunchKernelGGL(dev::k_refit_level, dim3((unsigned)((4 * (int64_t)T.count + 255) / 256)), dim3(256), 0, r.stream, T);
-    }
-    const int64_t n = (int64_t)L.nodes.size();
-    hipLaunchKernelGGL(dev::k_octant_copies, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, r.stream, r.wnodes, list, n,
-                       S.wide_copy);
-}
-
-// ---- deforming meshes (rtcore.h; deform.h) ------------------------------------------------------------
-// The BLAS an RT_OBJ_MESH object produced, through the retained object -> BLAS map (a mesh whose id
-// a MeshInstance took over has no instance of its own, but its BLAS is still used); -1: none
-static int32_t deform_blas_of(const rt_scene* s, int32_t object_index) {
-    const HostScene& S = s->host;
-    if (object_index < 0 || object_index >= (int32_t)S.object_blas.size()) return -1;
-    const int32_t b = S.object_blas[(size_t)object_index];
-    if (b < 0 || (size_t)b >= S.def.blas.size() || S.def.blas[(size_t)b].verts <= 0) return -1;
-    return b;
-}
-
-int32_t rt_scene_mesh_vertex_count(const rt_scene* s, int32_t object_index, int64_t* num_positions) {
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (!num_positions) return fail(RT_ERR_INVALID_ARG, "num_positions is NULL");
-    if (!s->host.deformable)
-        return fail(RT_ERR_UNSUPPORTED, "not a deformable scene (rt_scene_create_ex, RT_SCENE_DEFORMABLE)");
-    const int32_t b = deform_blas_of(s, object_index);
-    if (b < 0) return fail(RT_ERR_INVALID_ARG, "object is not a mesh with triangles");
-    *num_positions = s->host.def.blas[(size_t)b].verts;
-    return RT_OK;
-}
-
-int32_t rt_scene_set_mesh_positions(rt_scene* s, int32_t object_index, const double* positions, int64_t num_positions,
-                                    const double* normals, uint32_t flags) {
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (!s->host.deformable)
-        return fail(RT_ERR_UNSUPPORTED, "not a deformable scene (rt_scene_create_ex, RT_SCENE_DEFORMABLE)");
-    if (flags & ~RT_POSITIONS_DEVICE) return fail(RT_ERR_INVALID_ARG, "unknown flags");
-    const int32_t b = deform_blas_of(s, object_index);
-    if (b < 0) return fail(RT_ERR_INVALID_ARG, "object is not a mesh with triangles");
-    const DeformBlas& f = s->host.def.blas[(size_t)b];
-    if (!positions || num_positions != f.verts)
-        return fail(RT_ERR_INVALID_ARG, "num_positions must equal the mesh's vertex count");
-    if (normals && f.normals != kNormalsSupplied)
-        return fail(RT_ERR_INVALID_ARG, "the mesh derives its normals from its positions: normals must be NULL");
-    try {
-        rt_scene::StagedDeform sd;
-        sd.blas = b;
-        sd.has_nrm = normals != nullptr;
-        if (flags & RT_POSITIONS_DEVICE) {
-            for (const double* p : {positions, normals}) {
-                if (!p) continue;
-                hipPointerAttribute_t at{};
-                if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-                    (void)hipGetLastError();
-                    return fail(RT_ERR_UNSUPPORTED, "RT_POSITIONS_DEVICE: not a device pointer");
-                }
-                if (at.type != hipMemoryTypeDevice) return fail(RT_ERR_UNSUPPORTED, "RT_POSITIONS_DEVICE: not a device pointer");
-                for (const DeviceReplica& r : s->devs)
-                    if (r.device != at.device)
-                        return fail(RT_ERR_UNSUPPORTED, "RT_POSITIONS_DEVICE: every replica must be on the device that owns the buffer");
-            }
-            sd.dpos = positions;
-            sd.dnrm = normals;
-        } else {
-            sd.pos.assign(positions, positions + 3 * num_positions);
-            if (normals) sd.nrm.assign(normals, normals + 3 * num_positions);
-        }
-        std::lock_guard<std::mutex> lock(s->mu);
-        for (auto& e : s->staged_deform)
-            if (e.blas == b) { e = std::move(sd); return RT_OK; }
-        s->staged_deform.push_back(std::move(sd));
-        return RT_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(RT_ERR_OOM, "host allocation failed");
-    }
-}
-
-int32_t rt_scene_last_deform_stats(const rt_scene* s, rt_deform_stats* out) {
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
-    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
-    *out = s->last_deform;
-    return RT_OK;
-}
-
-// Commit scratch is touched by no render: it is replaced outright when it has to grow.
-static bool grow_plain(double** p, int64_t& cap, int64_t need) {
-    if (need <= cap && *p) return true;
-    (void)hipFree(*p);
-    *p = nullptr; cap = 0;
-    need = std::max<int64_t>(need, 1);
-    if (hipMalloc((void**)p, (size_t)need * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); *p = nullptr; return false; }
-    cap = need;
-    return true;
-}
-
-// ---- the flattened instance tree rebuilt for the committed pose (rtcore.h RT_COMMIT_REBUILD_FIT;
-// rebuild.h).  Every replica builds the new tree beside the old one on its own
-// stream; only when all of them hold a valid tree are the node arrays swapped, so a guard that
-// trips (depth, the 4 GB offset limit, an allocation) leaves every replica with the old tree.
-namespace {
-struct DevBuf {                                   // scratch of one rebuild: freed on every path
-    char* base = nullptr;
-    ~DevBuf() { (void)hipFree(base); }
-};
-struct RebuiltTree {                              // what one replica built
-    W4Node* wnodes = nullptr;                     // eight copies of main nodes + new fit nodes
-    int32_t* levels = nullptr;                    // the new fit_levels list on the device
-    std::vector<int64_t> level_count;             // nodes per level, root first
-    int64_t nodes = 0;
-    int32_t reason = RT_REBUILD_NONE;
-    double sort_ms = 0.0, build_ms = 0.0;
-    void drop() { (void)hipFree(wnodes); (void)hipFree(levels); wnodes = nullptr; levels = nullptr; }
-};
-}  // namespace
-
-static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t depth_cap, RebuiltTree& R) {
-    HIP_TRY(hipSetDevice(r.device));
-    const auto t0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point t) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-    };
-    const int64_t n = (int64_t)S.fpairs.size(), n_main = S.fit_root, old_copy = S.wide_copy;
-    const int64_t B = dev::kRbBlock;
-    auto grid = [&](int64_t items) { return dim3((unsigned)std::max<int64_t>(1, (items + B - 1) / B)); };
-    hipStream_t st = r.stream;
-    size_t sort_bytes = 0, scan_bytes = 0;
-    {
-        unsigned long long* k = nullptr;
-        uint32_t* v = nullptr;
-        int32_t* c = nullptr;
-        HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, k, k, v, v, (int)n, 0, 63, st));
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, c, c, (int)n, st));
-    }
-    const int parts = (int)std::min<int64_t>(dev::kRbParts, (n + B - 1) / B);
-    // one allocation, carved into 256-byte aligned parts: n pairs, n - 1 binary nodes, at most
-    // n - 1 four-wide nodes (each takes the subtree of a binary node of its own)
-    size_t total = 0;
-    auto take = [&](int64_t count, size_t elem) {
-        const size_t at = total;
-        total += ((size_t)std::max<int64_t>(count, 1) * elem + 255) & ~size_t(255);
-        return at;
-    };
-    const size_t o_pbox = take(6 * n, 8), o_partial = take(6 * (int64_t)parts, 8), o_ubox = take(6, 8), o_nbox = take(6 * n, 8),
-                 o_keys0 = take(n, 8), o_keys1 = take(n, 8), o_vals0 = take(n, 4), o_vals1 = take(n, 4), o_arrive = take(n, 4),
-                 o_left = take(n, 4), o_right = take(n, 4), o_parent = take(n, 4), o_leaf_parent = take(n, 4),
-                 o_cur = take(n, 4), o_next = take(n, 4), o_slots = take(4 * n, 4), o_cnt = take(n + 1, 4),
-                 o_off = take(n + 1, 4), o_wn = take(n, sizeof(W4Node)), o_sort = take((int64_t)sort_bytes, 1),
-                 o_scan = take((int64_t)scan_bytes, 1);
-    DevBuf buf;
-    if (hipMalloc((void**)&buf.base, total) != hipSuccess) {
-        (void)hipGetLastError();
-        buf.base = nullptr;
-        R.reason = RT_REBUILD_NO_MEMORY;
-        return RT_OK;
-    }
-    char* const m = buf.base;
-    double *pbox = (double*)(m + o_pbox), *partial = (double*)(m + o_partial), *ubox = (double*)(m + o_ubox),
-           *nbox = (double*)(m + o_nbox);
-    unsigned long long *keys0 = (unsigned long long*)(m + o_keys0), *keys1 = (unsigned long long*)(m + o_keys1);
-    uint32_t *vals0 = (uint32_t*)(m + o_vals0), *vals1 = (uint32_t*)(m + o_vals1);
-    unsigned* arrive = (unsigned*)(m + o_arrive);
-    int32_t *left = (int32_t*)(m + o_left), *right = (int32_t*)(m + o_right), *parent = (int32_t*)(m + o_parent),
-            *leaf_parent = (int32_t*)(m + o_leaf_parent), *cur = (int32_t*)(m + o_cur), *next = (int32_t*)(m + o_next),
-            *slots = (int32_t*)(m + o_slots), *cnt = (int32_t*)(m + o_cnt), *off = (int32_t*)(m + o_off);
-    W4Node* wn = (W4Node*)(m + o_wn);
-    void *sort_tmp = m + o_sort, *scan_tmp = m + o_scan;
-    // 1. pair boxes and their union, Morton codes, the stable sort
-    hipLaunchKernelGGL(dev::k_rb_pair_boxes, dim3((unsigned)parts), dim3(dev::kRbBlock), 0, st, (const DFitPair*)r.fpairs,
-                       (const double*)r.lbox, (const DInstance*)r.insts, n, pbox, partial);
-    hipLaunchKernelGGL(dev::k_rb_union, dim3(1), dim3(64), 0, st, (const double*)partial, parts, ubox);
-    hipLaunchKernelGGL(dev::k_rb_morton, grid(n), dim3(dev::kRbBlock), 0, st, (const double*)pbox, (const double*)ubox, n, keys0,
-                       vals0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipcub::DeviceRadixSort::SortPairs(sort_tmp, sort_bytes, keys0, keys1, vals0, vals1, (int)n, 0, 63, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    R.sort_ms = ms_since(t0);
-    const auto t1 = std::chrono::steady_clock::now();
-    // 2. the binary radix tree and its boxes
-    dev::RbTree T{};
-    T.keys = keys1; T.n = (int32_t)n; T.left = left; T.right = right; T.parent = parent; T.leaf_parent = leaf_parent;
-    HIP_TRY(hipMemsetAsync(arrive, 0, (size_t)n * sizeof(unsigned), st));
-    hipLaunchKernelGGL(dev::k_rb_hierarchy, grid(n - 1), dim3(dev::kRbBlock), 0, st, T);
-    hipLaunchKernelGGL(dev::k_rb_node_boxes, grid(n), dim3(dev::kRbBlock), 0, st, T, (const uint32_t*)vals1, (const double*)pbox,
-                       arrive, nbox);
-    HIP_TRY(hipGetLastError());
-    // 3. four-wide nodes, a level per pass: the level's nodes are wn[base, base + count)
-    HIP_TRY(hipMemsetAsync(cur, 0, sizeof(int32_t), st));                   // the root: binary node 0
-    int64_t base = 0, count = 1;
-    for (;;) {
-        if ((int64_t)R.level_count.size() + 1 > depth_cap) { R.reason = RT_REBUILD_TOO_DEEP; return RT_OK; }
-        if (8 * (size_t)(n_main + base + count) * sizeof(W4Node) >= (size_t(1) << 32)) { R.reason = RT_REBUILD_TOO_LARGE; return RT_OK; }
-        if (base + count > n - 1) return fail(RT_ERR_DEVICE, "rebuild: more four-wide nodes than binary nodes");
-        dev::RbLevel L{};
-        L.left = left; L.right = right; L.nbox = nbox; L.pbox = pbox; L.sorted = vals1; L.cur = cur; L.count = (int32_t)count;
-        L.slots = slots; L.cnt = cnt; L.off = off; L.next = next; L.nodes = wn + base;
-        L.child_base = (int32_t)(n_main + base + count);
-        hipLaunchKernelGGL(dev::k_rb_collapse, grid(count + 1), dim3(dev::kRbBlock), 0, st, L);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, cnt, off, (int)(count + 1), st));
-        hipLaunchKernelGGL(dev::k_rb_emit, grid(4 * count), dim3(dev::kRbBlock), 0, st, L);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(st));
-        int32_t total = 0;
-        HIP_TRY(hipMemcpy(&total, off + count, sizeof(total), hipMemcpyDeviceToHost));
-        R.level_count.push_back(count);
-        base += count;
-        if (total <= 0) break;
-        count = total;
-        std::swap(cur, next);
-    }
-    R.nodes = base;
-    // 4. the new node array: the eight main parts as they are, the new fit nodes behind copy 0's,
-    //    then their octant copies (refit.h k_octant_copies over the level list, deepest level first)
-    const int64_t new_copy = n_main + R.nodes;
-    if (hipMalloc((void**)&R.wnodes, (size_t)(8 * new_copy) * sizeof(W4Node)) != hipSuccess ||
-        hipMalloc((void**)&R.levels, (size_t)R.nodes * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
-        R.drop();
-        R.reason = RT_REBUILD_NO_MEMORY;
-        return RT_OK;
-    }
-    for (int o = 0; o < 8 && n_main > 0; ++o)
-        HIP_TRY(hipMemcpyAsync(R.wnodes + (size_t)o * new_copy, r.wnodes + (size_t)o * old_copy, (size_t)n_main * sizeof(W4Node),
-                               hipMemcpyDeviceToDevice, st));
-    HIP_TRY(hipMemcpyAsync(R.wnodes + n_main, wn, (size_t)R.nodes * sizeof(W4Node), hipMemcpyDeviceToDevice, st));
-    std::vector<int32_t> list;
-    list.reserve((size_t)R.nodes);
-    {
-        int64_t end = n_main + R.nodes;
-        for (size_t l = R.level_count.size(); l-- > 0;) {
-            const int64_t first = end - R.level_count[l];
-            for (int64_t k = first; k < end; ++k) list.push_back((int32_t)k);
-            end = first;
-        }
-    }
-    HIP_TRY(hipMemcpyAsync(R.levels, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(dev::k_octant_copies, grid(R.nodes), dim3(256), 0, st, R.wnodes, (const int32_t*)R.levels, R.nodes, new_copy);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(st));
-    R.build_ms = ms_since(t1);
-    return RT_OK;
-}
-
-// The rebuild step of a commit (the scene lock is held, no render is in flight).  Returns RT_OK
-// also when nothing was rebuilt (s->last_rebuild says why); an error only for a device failure.
-static int32_t rebuild_fit(rt_scene* s) {
-    const auto t0 = std::chrono::steady_clock::now();
-    HostScene& S = s->host;
-    rt_rebuild_stats st{};
-    const bool has = S.fit_root >= 0 && S.wide_copy > 0 && !S.winst.empty();
-    st.pairs = has ? (int64_t)S.fpairs.size() : 0;
-    st.nodes_before = st.nodes_after = has ? S.fit_nodes : 0;
-    st.depth_before = st.depth_after = has ? S.fit_depth : 0;
-    auto done = [&](int32_t reason) {
-        st.reason = reason;
-        st.rebuilt = reason == RT_REBUILD_NONE ? 1 : 0;
-        st.total_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        s->last_rebuild = st;
-        return (int32_t)RT_OK;
-    };
-    bool tree = has && S.fpairs.size() >= 2 && S.fpairs.size() < (size_t(1) << 30);
-    for (const DeviceReplica& r : s->devs) tree = tree && r.wnodes && r.fpairs && r.lbox && r.insts;
-    if (!tree) return done(RT_REBUILD_NO_TREE);
-    if (S.dyn.fit_blocked) return done(RT_REBUILD_BLOCKED);
-    try {
-        std::vector<RebuiltTree> res(s->devs.size());
-        auto drop_all = [&]() {
-            for (size_t k = 0; k < res.size(); ++k) {
-                (void)hipSetDevice(s->devs[k].device);
-                res[k].drop();
-            }
-        };
-        for (size_t k = 0; k < res.size(); ++k) {
-            const int32_t rc = rebuild_fit_on(S, s->devs[k], s->opt[kOptRebuildDepthCap], res[k]);
-            if (rc == RT_OK && res[k].reason == RT_REBUILD_NONE && res[k].level_count == res[0].level_count) continue;
-            const int32_t reason = res[k].reason;
-            drop_all();
-            if (rc != RT_OK) return rc;
-            if (reason != RT_REBUILD_NONE) return done(reason);
-            return fail(RT_ERR_DEVICE, "rebuild: the replicas built different trees");
-        }
-        for (size_t k = 0; k < res.size(); ++k) {
-            DeviceReplica& r = s->devs[k];
-            HIP_TRY(hipSetDevice(r.device));
-            (void)hipFree(r.wnodes);                        // no kernel holds it: commits do not run beside renders
-            (void)hipFree(r.fit_levels);
-            r.wnodes = res[k].wnodes;
-            r.fit_levels = res[k].levels;
-            r.bytes += (8 * (res[k].nodes - S.fit_nodes)) * (int64_t)sizeof(W4Node) +
-                       (res[k].nodes - (int64_t)std::max<size_t>(1, S.dyn.fit_levels.nodes.size())) * (int64_t)sizeof(int32_t);
-            st.sort_ms = std::max(st.sort_ms, res[k].sort_ms);
-            st.build_ms = std::max(st.build_ms, res[k].build_ms);
-        }
-        // what the host keeps: the counts renders and queries are made from, and the level lists
-        // a later plain commit refits
-        const RebuiltTree& R0 = res[0];
-        RefitLevels& L = S.dyn.fit_levels;
-        L.nodes.clear(); L.off.clear();
-        int64_t end = S.fit_root + R0.nodes;
-        for (size_t l = R0.level_count.size(); l-- > 0;) {
-            L.off.push_back((int64_t)L.nodes.size());
-            for (int64_t k = end - R0.level_count[l]; k < end; ++k) L.nodes.push_back((int32_t)k);
-            end -= R0.level_count[l];
-        }
-        L.off.push_back((int64_t)L.nodes.size());
-        S.wide_copy = S.fit_root + R0.nodes;
-        S.fit_nodes = R0.nodes;
-        S.fit_depth = (int64_t)R0.level_count.size();
-        st.nodes_after = S.fit_nodes;
-        st.depth_after = S.fit_depth;
-        return done(RT_REBUILD_NONE);
-    } catch (const std::bad_alloc&) {
-        return fail(RT_ERR_OOM, "host allocation failed");
-    }
-}
-
-static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats);
-
-int32_t rt_scene_commit(rt_scene* s, rt_commit_stats* stats) { return commit_impl(s, 0u, stats); }
-
-int32_t rt_scene_commit_ex(rt_scene* s, uint32_t flags, rt_commit_stats* stats) { return commit_impl(s, flags, stats); }
-
-int32_t rt_scene_last_rebuild_stats(const rt_scene* s, rt_rebuild_stats* out) {
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
-    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
-    *out = s->last_rebuild;
-    return RT_OK;
-}
-
-static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) {
-    if (stats) *stats = rt_commit_stats{};
-    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (flags & ~RT_COMMIT_REBUILD_FIT) return fail(RT_ERR_INVALID_ARG, "unknown commit flags");
-    const bool rebuild = (flags & RT_COMMIT_REBUILD_FIT) != 0;
-    if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
-    std::lock_guard<std::mutex> lock(s->mu);
-    if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
-    const auto t0 = std::chrono::steady_clock::now();
-    auto ms_since = [](std::chrono::steady_clock::time_point t) {
-        return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count();
-    };
-    s->last_deform = rt_deform_stats{};
-    if (s->staged.empty() && s->staged_deform.empty()) {
-        int32_t rc = RT_OK;
-        if (rebuild) {                                       // nothing staged: the pose as it stands
-            rc = rebuild_fit(s);
-            if (rc == RT_OK) drop_tile_orders(s);
-        } else {
-            s->last_rebuild = rt_rebuild_stats{};
-        }
-        if (stats) stats->total_ms = ms_since(t0);
-        return rc;
-    }
-    try {
-        HostScene& S = s->host;
-        DynScene& Y = S.dyn;
-        const DeformScene& F = S.def;
-        std::vector<std::pair<int32_t, std::array<double, 16>>> staged;
-        staged.swap(s->staged);                              // a failed commit stages nothing
-        std::vector<rt_scene::StagedDeform> sdef;
-        sdef.swap(s->staged_deform);
-        const size_t n = staged.size(), nd = sdef.size();
-        const bool has_wide = !S.winst.empty();
-        rt_deform_stats dst{};
-        // the matrix instance k has once this commit is through
-        auto matrix_of = [&](int32_t k) -> const double* {
-            for (const auto& e : staged)
-                if (e.first == k) return e.second.data();
-            return S.insts[(size_t)k].l2w;
-        };
-        std::vector<char> deformed(Y.blas.size(), 0);
-        for (const auto& sd : sdef) deformed[(size_t)sd.blas] = 1;
-        int32_t rc = RT_OK;
-
-        // 0. staged positions: on the device, then checked there before anything changes (deform.h
-        //    k_deform_validate).  Host arrays go to one staging buffer per replica.
-        std::vector<int64_t> pos_off(nd, 0), nrm_off(nd, 0), part_off(nd, 0);
-        int64_t stage_total = 0, part_total = 2 * dev::kValidateParts, face_need = 0, vnorm_need = 0;
-        {
-            int64_t blocks = 0;
-            for (size_t m = 0; m < nd; ++m) {
-                const rt_scene::StagedDeform& sd = sdef[m];
-                const DeformBlas& f = F.blas[(size_t)sd.blas];
-                const DynBlas& y = Y.blas[(size_t)sd.blas];
-                pos_off[m] = stage_total; stage_total += (int64_t)sd.pos.size();
-                nrm_off[m] = stage_total; stage_total += (int64_t)sd.nrm.size();
-                part_off[m] = blocks;
-                blocks += (y.tri_end - y.tri_first + dev::kDeformBlock - 1) / dev::kDeformBlock;
-                if (f.normals == kNormalsSmooth) {
-                    face_need = std::max(face_need, 3 * (y.tri_end - y.tri_first));
-                    vnorm_need = std::max(vnorm_need, 3 * f.verts);
-                }
-                dst.triangles += y.tri_end - y.tri_first;
-            }
-            part_total = std::max(part_total, blocks);
-        }
-        auto stage_replica = [&](DeviceReplica& r) -> int32_t {
-            HIP_TRY(hipSetDevice(r.device));
-            if (!grow_plain(&r.def_stage, r.def_stage_cap, stage_total) || !grow_plain(&r.def_part, r.def_part_cap, part_total) ||
-                !grow_plain(&r.def_out, r.def_out_cap, 8 * (int64_t)nd) || !grow_plain(&r.def_face, r.def_face_cap, face_need) ||
-                !grow_plain(&r.def_vnorm, r.def_vnorm_cap, vnorm_need))
-                return fail(RT_ERR_OOM, "device allocation failed (deformation scratch)");
-            for (size_t m = 0; m < nd; ++m) {
-                const rt_scene::StagedDeform& sd = sdef[m];
-                if (!sd.pos.empty())
-                    HIP_TRY(hipMemcpy(r.def_stage + pos_off[m], sd.pos.data(), sd.pos.size() * sizeof(double), hipMemcpyHostToDevice));
-                if (!sd.nrm.empty())
-                    HIP_TRY(hipMemcpy(r.def_stage + nrm_off[m], sd.nrm.data(), sd.nrm.size() * sizeof(double), hipMemcpyHostToDevice));
-            }
-            return RT_OK;
-        };
-        auto pos_ptr = [&](const DeviceReplica& r, size_t m) -> const double* {
-            return sdef[m].dpos ? sdef[m].dpos : r.def_stage + pos_off[m];
-        };
-        auto nrm_ptr = [&](const DeviceReplica& r, size_t m) -> const double* {
-            if (!sdef[m].has_nrm) return nullptr;
-            return sdef[m].dnrm ? sdef[m].dnrm : r.def_stage + nrm_off[m];
-        };
-        if (nd > 0) {
-            DeviceReplica& r = s->devs[0];
-            if ((rc = stage_replica(r)) != RT_OK) return rc;
-            for (size_t m = 0; m < nd; ++m) {
-                const int64_t n3 = 3 * F.blas[(size_t)sdef[m].blas].verts;
-                const int parts = (int)std::max<int64_t>(1, std::min<int64_t>(dev::kValidateParts, (n3 + dev::kDeformBlock - 1) / dev::kDeformBlock));
-                hipLaunchKernelGGL(dev::k_deform_validate, dim3((unsigned)parts), dim3(dev::kDeformBlock), 0, r.stream,
-                                   pos_ptr(r, m), n3, r.def_part);
-                hipLaunchKernelGGL(dev::k_deform_validate_final, dim3(1), dim3(64), 0, r.stream, r.def_part, parts,
-                                   r.def_out + 2 * m);
-            }
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(r.stream));
-            std::vector<double> v(2 * nd, 0.0);
-            HIP_TRY(hipMemcpy(v.data(), r.def_out, v.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (size_t m = 0; m < nd; ++m) {
-                if (!(v[2 * m] == 1.0)) return fail(RT_ERR_INVALID_ARG, "staged positions are not all finite");
-                const DynBlas& y = Y.blas[(size_t)sdef[m].blas];
-                const double c = v[2 * m + 1] + std::fmax(std::fabs(y.motion[0]), std::fmax(std::fabs(y.motion[1]), std::fabs(y.motion[2])));
-                for (size_t i = 0; i < Y.inst_blas.size(); ++i) {
-                    if (Y.inst_blas[i] != sdef[m].blas) continue;
-                    const double* mt = matrix_of((int32_t)i);
-                    double reach = 0.0;
-                    for (int a = 0; a < 16; ++a) reach = std::max(reach, std::fabs(mt[a]));
-                    if (!(reach * (3.0 * c + 1.0) < 1e30))
-                        return fail(RT_ERR_INVALID_ARG, "staged positions put an instance of the mesh out of range");
-                }
-            }
-            dst.validate_ms = ms_since(t0);
-        }
-        // 1. Instance.worldBounds of the moved instances: triangle meshes on the device (the union
-        //    over every triangle), spheres and planes (one primitive) here.  Instances of a deformed
-        //    mesh wait for its new triangle boxes (step 2c); their range is settled by step 0.
-        const auto tb0 = std::chrono::steady_clock::now();
-        std::vector<double> nb(6 * n, 0.0), devb;
-        std::vector<dev::RefitMove> moves;
-        std::vector<size_t> move_of;
-        std::vector<char> later(n, 0);
-        auto move_for = [&](int32_t k, const double* m16) {
-            const DynBlas& y = Y.blas[(size_t)Y.inst_blas[(size_t)k]];
-            dev::RefitMove mv{};
-            std::memcpy(mv.m, m16, sizeof(mv.m));
-            for (int a = 0; a < 3; ++a) mv.motion[a] = y.motion[a];
-            mv.tri_first = (int32_t)y.tri_first; mv.tri_end = (int32_t)y.tri_end;
-            mv.blur = !(y.motion[0] == 0 && y.motion[1] == 0 && y.motion[2] == 0) ? 1 : 0;
-            return mv;
-        };
-        for (size_t q = 0; q < n; ++q) {
-            const int32_t k = staged[q].first;
-            const DynBlas& y = Y.blas[(size_t)Y.inst_blas[(size_t)k]];
-            if (y.kind != kPrimTriangles) {
-                special_instance_bounds(S, k, staged[q].second.data(), &nb[6 * q], &nb[6 * q + 3]);
-                continue;
-            }
-            if (deformed[(size_t)Y.inst_blas[(size_t)k]]) { later[q] = 1; continue; }
-            moves.push_back(move_for(k, staged[q].second.data()));
-            move_of.push_back(q);
-        }
-        rc = device_instance_bounds(s, moves, devb);
-        if (rc != RT_OK) return rc;
-        for (size_t j = 0; j < move_of.size(); ++j) std::memcpy(&nb[6 * move_of[j]], &devb[6 * j], 6 * sizeof(double));
-        double bounds_ms = ms_since(tb0);
-        // 2. nothing is changed unless every moved instance stays in range (float boxes stay finite)
-        for (size_t q = 0; q < n; ++q) {
-            if (later[q]) continue;
-            bool ok = true;
-            for (int a = 0; a < 6; ++a) ok = ok && std::isfinite(nb[6 * q + a]) && std::fabs(nb[6 * q + a]) < 1e30;
-            if (!S.winst.empty()) {
-                const double* m = staged[q].second.data();
-                double reach = 0.0;
-                for (int a = 0; a < 16; ++a) reach = std::max(reach, std::fabs(m[a]));
-                ok = ok && reach * (3.0 * S.winst[(size_t)staged[q].first].bcoord + 1.0) < 1e30;
-            }
-            if (!ok) return fail(RT_ERR_INVALID_ARG, "a staged transform puts its instance out of range");
-        }
-        // 2a-c. the deformations (deform.h), the same kernels on every replica's stream: triangles,
-        //    triangle boxes, normals and leaf boxes; then the BLAS records and four-wide nodes level by
-        //    level; replica 0's root boxes and |e1||e2| come back to the host, and the instances of the
-        //    deformed meshes take new world bounds from the new triangle boxes
-        std::vector<std::pair<int32_t, std::array<double, 6>>> rebound;
-        if (nd > 0) {
-            const auto td0 = std::chrono::steady_clock::now();
-            auto run_of = [&](const DeviceReplica& r, const DynBlas& y) {
-                dev::DeformRun R{};
-                R.tris = r.tris; R.pbox = r.pbox; R.tri_end = (int32_t)y.tri_end;
-                R.blur = !(y.motion[0] == 0 && y.motion[1] == 0 && y.motion[2] == 0) ? 1 : 0;
-                for (int a = 0; a < 3; ++a) R.motion[a] = y.motion[a];
-                return R;
-            };
-            auto grid = [](int64_t items) { return dim3((unsigned)std::max<int64_t>(1, (items + dev::kDeformBlock - 1) / dev::kDeformBlock)); };
-            for (DeviceReplica& r : s->devs) {
-                if (&r != &s->devs[0] && (rc = stage_replica(r)) != RT_OK) return rc;
-                HIP_TRY(hipSetDevice(r.device));
-                if (!r.pbox || !r.vid) return fail(RT_ERR_DEVICE, "deformable scene without triangle boxes");
-                for (size_t m = 0; m < nd; ++m) {
-                    const DeformBlas& f = F.blas[(size_t)sdef[m].blas];
-                    const DynBlas& y = Y.blas[(size_t)sdef[m].blas];
-                    const int64_t nt = y.tri_end - y.tri_first;
-                    dev::DeformMesh M{};
-                    M.pos = pos_ptr(r, m); M.vid = r.vid;
-                    const double* new_nrm = nrm_ptr(r, m);       // newly supplied per-vertex normals, or null
-                    M.tri_first = (int32_t)y.tri_first; M.tri_end = (int32_t)y.tri_end;
-                    M.prim_base = f.prim_base; M.normals = f.normals;
-                    const dev::DeformRun R = run_of(r, y);
-                    hipLaunchKernelGGL(dev::k_deform_tris, grid(nt), dim3(dev::kDeformBlock), 0, r.stream, M, r.tris, r.pbox,
-                                       r.normals, r.def_face, r.def_part + part_off[m]);
-                    if (f.normals == kNormalsSmooth) {
-                        hipLaunchKernelGGL(dev::k_vertex_normals, grid(f.verts), dim3(dev::kDeformBlock), 0, r.stream,
-                                           r.csr_off + f.csr_off_first, r.csr_tri + f.csr_first, f.verts, r.def_face, r.def_vnorm);
-                        hipLaunchKernelGGL(dev::k_gather_normals, grid(nt), dim3(dev::kDeformBlock), 0, r.stream, r.vid,
-                                           M.tri_first, M.tri_end, (const double*)r.def_vnorm, r.normals);
-                    } else if (f.normals == kNormalsSupplied && new_nrm) {
-                        hipLaunchKernelGGL(dev::k_gather_normals, grid(nt), dim3(dev::kDeformBlock), 0, r.stream, r.vid,
-                                           M.tri_first, M.tri_end, new_nrm, r.normals);
-                    }
-                    if (has_wide)
-                        hipLaunchKernelGGL(dev::k_leaf_boxes, grid(nt), dim3(dev::kDeformBlock), 0, r.stream, R, M.tri_first, r.lbox);
-                }
-                HIP_TRY(hipGetLastError());
-            }
-            for (DeviceReplica& r : s->devs) {
-                HIP_TRY(hipSetDevice(r.device));
-                HIP_TRY(hipStreamSynchronize(r.stream));
-            }
-            dst.deform_ms = ms_since(td0);
-            const auto tr0 = std::chrono::steady_clock::now();
-            for (DeviceReplica& r : s->devs) {
-                HIP_TRY(hipSetDevice(r.device));
-                for (size_t m = 0; m < nd; ++m) {
-                    const DeformBlas& f = F.blas[(size_t)sdef[m].blas];
-                    const DynBlas& y = Y.blas[(size_t)sdef[m].blas];
-                    const int64_t nt = y.tri_end - y.tri_first;
-                    const dev::DeformRun R = run_of(r, y);
-                    for (size_t l = 0; l + 1 < f.rec_off.size(); ++l) {
-                        const int32_t cnt = (int32_t)(f.rec_off[l + 1] - f.rec_off[l]);
-                        if (cnt <= 0) continue;
-                        hipLaunchKernelGGL(dev::k_refit_recs, grid(2 * (int64_t)cnt), dim3(dev::kDeformBlock), 0, r.stream, r.recs,
-                                           (const int32_t*)(r.rec_list + f.rec_off[l]), cnt, R);
-                    }
-                    hipLaunchKernelGGL(dev::k_blas_root, dim3(1), dim3(64), 0, r.stream, (const WRec*)r.recs, f.root_ref, R,
-                                       (const double*)(r.def_part + part_off[m]),
-                                       (int)((nt + dev::kDeformBlock - 1) / dev::kDeformBlock), r.def_out + 8 * m);
-                    if (has_wide && r.wnodes && f.wroot >= 0 && f.wide_off.size() > 1) {
-                        for (size_t l = 0; l + 1 < f.wide_off.size(); ++l) {
-                            const int32_t cnt = (int32_t)(f.wide_off[l + 1] - f.wide_off[l]);
-                            if (cnt <= 0) continue;
-                            hipLaunchKernelGGL(dev::k_refit_blas_level, grid(4 * (int64_t)cnt), dim3(dev::kDeformBlock), 0, r.stream,
-                                               r.wnodes, (const int32_t*)(r.wide_list + f.wide_off[l]), cnt, (const double*)r.lbox);
-                        }
-                        const int64_t nn = f.wide_off.back() - f.wide_off.front();
-                        hipLaunchKernelGGL(dev::k_octant_copies, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, r.stream, r.wnodes,
-                                           (const int32_t*)(r.wide_list + f.wide_off.front()), nn, S.wide_copy);
-                    }
-                }
-                HIP_TRY(hipGetLastError());
-            }
-            for (DeviceReplica& r : s->devs) {
-                HIP_TRY(hipSetDevice(r.device));
-                HIP_TRY(hipStreamSynchronize(r.stream));
-            }
-            std::vector<double> roots(8 * nd, 0.0);
-            HIP_TRY(hipSetDevice(s->devs[0].device));
-            HIP_TRY(hipMemcpy(roots.data(), s->devs[0].def_out, roots.size() * sizeof(double), hipMemcpyDeviceToHost));
-            dst.blas_refit_ms = ms_since(tr0);
-            // the host's copies: the pruning margin's constant, the BLAS root box of every instance of
-            // the mesh and the widening bound of its local rays (scene.cpp build_wide_tw: bcoord)
-            const auto tb1 = std::chrono::steady_clock::now();
-            std::vector<dev::RefitMove> dmoves;
-            std::vector<int32_t> dinst;
-            for (size_t m = 0; m < nd; ++m) {
-                const double* o = &roots[8 * m];
-                Y.blas[(size_t)sdef[m].blas].P = o[6];
-                double bc = 0.0;
-                for (int a = 0; a < 6; ++a) bc = std::fmax(bc, std::fabs(o[a]));
-                for (size_t i = 0; i < Y.inst_blas.size(); ++i) {
-                    if (Y.inst_blas[i] != sdef[m].blas) continue;
-                    DInstance& di = S.insts[i];
-                    for (int a = 0; a < 3; ++a) { di.root_lo[a] = o[a]; di.root_hi[a] = o[3 + a]; }
-                    if (has_wide) S.winst[i].bcoord = bc;
-                    dmoves.push_back(move_for((int32_t)i, matrix_of((int32_t)i)));
-                    dinst.push_back((int32_t)i);
-                }
-            }
-            std::vector<double> db;
-            rc = device_instance_bounds(s, dmoves, db);
-            if (rc != RT_OK) return rc;
-            for (size_t j = 0; j < dinst.size(); ++j) {
-                std::array<double, 6> b6;
-                std::memcpy(b6.data(), &db[6 * j], sizeof(b6));
-                rebound.push_back({dinst[j], b6});
-            }
-            bounds_ms += ms_since(tb1);
-            dst.meshes_deformed = (int64_t)nd;
-            dst.instances_rebounded = (int64_t)dinst.size();
-        }
-        // 3. host: DInstance, TLAS bounds bottom-up, TLAS records, tbox, the margins' constants
-        const auto t1 = std::chrono::steady_clock::now();
-        for (size_t q = 0; q < n; ++q) {
-            set_instance_matrix(S, staged[q].first, staged[q].second.data());
-            if (!later[q]) std::memcpy(&S.inst_bounds[6 * (size_t)staged[q].first], &nb[6 * q], 6 * sizeof(double));
-        }
-        for (const auto& e : rebound) std::memcpy(&S.inst_bounds[6 * (size_t)e.first], e.second.data(), 6 * sizeof(double));
-        std::string err;
-        rc = refit_host_scene(S, err);
-        if (rc != RT_OK) return fail(rc, err);
-        // 4. every replica: instances, TLAS records, tbox; then the four-wide trees on its stream
-        for (DeviceReplica& r : s->devs) {
-            HIP_TRY(hipSetDevice(r.device));
-            HIP_TRY(hipMemcpy(r.insts, S.insts.data(), S.insts.size() * sizeof(DInstance), hipMemcpyHostToDevice));
-            if (!Y.tlas_recs.empty())
-                HIP_TRY(hipMemcpy(r.recs + S.blas_records, Y.tlas_recs.data(), Y.tlas_recs.size() * sizeof(WRec),
-                                  hipMemcpyHostToDevice));
-            if (!S.winst.empty() && r.wnodes) {
-                HIP_TRY(hipMemcpy(r.winst, S.winst.data(), S.winst.size() * sizeof(DWideInst), hipMemcpyHostToDevice));
-                refit_tree(S, r, Y.tlas_levels, r.tlas_levels, (int32_t)(S.tlas_leaf_base + (int64_t)S.tlas_leaf.size()));
-                if (S.fit_root >= 0) refit_tree(S, r, Y.fit_levels, r.fit_levels, -1);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-        for (DeviceReplica& r : s->devs) {
-            HIP_TRY(hipSetDevice(r.device));
-            HIP_TRY(hipStreamSynchronize(r.stream));
-        }
-        drop_tile_orders(s);
-        s->last_deform = dst;
-        const double refit_ms = ms_since(t1);
-        // 5. on request the flattened instance tree again, from the pose just committed
-        if (rebuild) {
-            if ((rc = rebuild_fit(s)) != RT_OK) return rc;
-        } else {
-            s->last_rebuild = rt_rebuild_stats{};
-        }
-        if (stats) {
-            stats->instances_moved = (int64_t)n;
-            stats->bounds_ms = bounds_ms;
-            stats->refit_ms = refit_ms;
-            stats->total_ms = ms_since(t0);
-        }
-        return RT_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(RT_ERR_OOM, "host allocation failed");
-    } catch (const std::exception& e) {
-        return fail(RT_ERR_INVALID_ARG, e.what());
-    }
-}
+extern "C" {
 
 int32_t rt_render_device(rt_scene* s, int32_t slot, int32_t cam, int32_t first, int32_t step, double* d_rgb,
                          uint8_t* d_rgba8, void* stream) {

@@ -45,7 +45,7 @@ struct HostCamera { rt_camera c; };
 // BVHBuilder.refit does, BVH.swift:254-291); and, for the four-wide TLAS nodes and the flattened
 // instance tree, the nodes of every level, deepest level first (the device refits a level per
 // launch, refit.h).  fit_levels is replaced when a commit rebuilds the flattened instance tree
-// (render.hip rebuild_fit): the next plain commit refits the new topology.
+// (commit.h rebuild_fit): the next plain commit refits the new topology.
 struct DynBlas {
     int64_t tri_first = 0, tri_end = 0;
     int32_t kind = kPrimTriangles;
