@@ -180,6 +180,24 @@ public:
         check(rt_scene_last_rebuild_stats(scene_, &st));
         return st;
     }
+    /* commitEx(RT_COMMIT_REBUILD_FIT_CLUSTERED) rebuilds with the clustered builder; lastRebuildDetail()
+     * says which builder made the tree and what it cost before and after; fitCost() is the cost of
+     * the tree in use now (lower is better; 0 without such a tree). */
+    rt_commit_stats commitEx(uint32_t flags) {
+        rt_commit_stats st{};
+        check(rt_scene_commit_ex(scene_, flags, &st));
+        return st;
+    }
+    rt_rebuild_detail lastRebuildDetail() const {
+        rt_rebuild_detail st{};
+        check(rt_scene_last_rebuild_detail(scene_, &st));
+        return st;
+    }
+    double fitCost() {
+        double c = 0.0;
+        check(rt_scene_fit_cost(scene_, &c));
+        return c;
+    }
     /* Deforming meshes (an engine built with `deformable`, which implies `dynamic`): BVHBuilder.refit
      * (BVH.swift:254-291) applied to a BLAS on the device.  setPositions stages xyz triples (and, for a
      * mesh created with per-vertex normals, optionally new normals) for mesh object `objectIndex`

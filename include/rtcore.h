@@ -313,11 +313,23 @@ int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);
  * travel; rt_scene_commit_ex with RT_COMMIT_REBUILD_FIT builds it again on the device for the
  * committed pose (Morton order of the pairs' world boxes, a binary radix tree, collapsed to
  * four-wide nodes: myraytracer_amd/csrc/rebuild.h).  The caller decides when: there is no automatic
- * policy.  Measured on C3i: a rebuilding commit costs 4.5 ms against 0.36 ms for a
- * plain one and 520 to 580 ms for a new rt_scene_create.  A Morton-order tree is worth 0.67 to 0.79
- * of the host's SAH tree there, so the rebuilt tree renders SLOWER than the refit one while the
- * instances have moved by up to four of their own diameters (0.86 to 0.88 of it); a rebuild pays
- * from somewhere between four and eight diameters (1.20 times at eight, 2.27 times at sixteen).
+ * policy; rt_scene_fit_cost gives the number to decide by.  Measured on C3i:
+ * a plain commit takes 0.37 ms, a rebuilding one 4.7 ms with the Morton builder and 4.9 ms with the
+ * clustered one (54 to 60 iterations over 562,033 pairs), a new rt_scene_create 510 to 580 ms.  The
+ * Morton tree is worth 0.67 to 0.79 of the host's SAH tree there, the clustered one 0.82 to 0.89.  A
+ * rebuilt tree of EITHER builder still renders SLOWER than the refit one while the instances have
+ * moved by up to four of their own diameters: Morton 0.86 and 0.89 of it at one and four diameters,
+ * clustered 0.96 and 0.99.  From eight diameters a rebuild pays: Morton 1.20 times at eight and 2.28
+ * times at sixteen, clustered 1.32 and 2.79 times.  rt_rebuild_detail's costs tell the cases apart
+ * roughly, not exactly: at one diameter the clustered rebuild raised the cost (18.5 to 20.0), at four
+ * it lowered it by 2 % and still rendered 1.5 % slower, at sixteen it lowered it from 31.6 to 7.5.
+ * Two builders make the binary tree that is collapsed: RT_COMMIT_REBUILD_FIT takes the radix tree
+ * over the Morton codes; RT_COMMIT_REBUILD_FIT_CLUSTERED (alone or together with it) clusters the
+ * Morton-sorted pairs instead (parallel locally-ordered clustering: every cluster merges with the
+ * neighbour, up to 16 positions away, whose union box with it is smallest, while both agree - DESIGN.md
+ * §13).  Both are deterministic: the tree depends on the committed pose only.  A clustering that has
+ * not finished after 4 ceil(log2 pairs) + 32 iterations (or the test hook rebuild_cluster_iter_cap)
+ * is given up and the Morton tree built instead: no error, rt_rebuild_detail.fell_back = 1.
  *   rt_scene_commit_ex   rt_scene_commit with flags (rt_scene_commit == flags 0).  Staged transforms
  *       and positions are validated and applied exactly as by rt_scene_commit - a refused commit
  *       rebuilds nothing and leaves the last rebuild's stats as they were - then the tree is rebuilt
@@ -331,10 +343,19 @@ int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);
  *       array would reach 4 GB, or when a device allocation fails.  The old tree then stays in place,
  *       refit as by a plain commit.
  *   rt_scene_last_rebuild_stats   what the last successful commit did for a rebuild (zeros when it
- *       asked for none).  rt_commit_stats.total_ms includes the rebuild.
+ *       asked for none).  rt_commit_stats.total_ms includes the rebuild; build_ms includes the clustering.
+ *   rt_scene_last_rebuild_detail  which builder made the tree of that commit (zeros when it asked for
+ *       no rebuild; builder = 0 and cost_after = cost_before when the old tree stayed), how many
+ *       iterations the clustering took, and the tree's cost before and after.
+ *   rt_scene_fit_cost    the cost of the tree in use now, on replica 0: the sum, over the non-empty
+ *       slots of its nodes, of the slot box's surface area, over the area of the union of the root's
+ *       slots (lower is better; what a ray pays grows with it).  Summed in a fixed order: the value
+ *       depends on the tree only.  RT_OK with cost 0 when the scene has no such tree;
+ *       RT_ERR_UNSUPPORTED without RT_SCENE_DYNAMIC, RT_ERR_BUSY as rt_scene_commit.
  * Not rebuilt: the reference-form TLAS, the BLASes, the TLAS's four-wide marker tree (option fit = 0).
  * Instances can still not be added or removed. */
 #define RT_COMMIT_REBUILD_FIT 1u
+#define RT_COMMIT_REBUILD_FIT_CLUSTERED 8u   /* rebuild with the clustered builder (bits 2 and 4 stay unknown) */
 #define RT_REBUILD_NONE        0    /* rt_rebuild_stats.reason: rebuilt, or no rebuild asked for */
 #define RT_REBUILD_NO_TREE     1
 #define RT_REBUILD_BLOCKED     2
@@ -353,6 +374,16 @@ typedef struct rt_rebuild_stats {
 } rt_rebuild_stats;
 int32_t rt_scene_commit_ex(rt_scene* scene, uint32_t flags, rt_commit_stats* stats /* may be NULL */);
 int32_t rt_scene_last_rebuild_stats(const rt_scene* scene, rt_rebuild_stats* out);
+typedef struct rt_rebuild_detail {
+    int32_t builder;            /* 0: none, 1: Morton radix tree, 2: clustered             */
+    int32_t iterations;         /* of the clustering                                       */
+    int32_t fell_back;          /* 1: the clustering was given up, the Morton tree built   */
+    int32_t pad;
+    double  cluster_ms;         /* the clustering (part of rt_rebuild_stats.build_ms)      */
+    double  cost_before, cost_after;   /* rt_scene_fit_cost around the rebuild             */
+} rt_rebuild_detail;
+int32_t rt_scene_last_rebuild_detail(const rt_scene* scene, rt_rebuild_detail* out);
+int32_t rt_scene_fit_cost(rt_scene* scene, double* cost);
 
 /* Render options: tuning and test switches, each default being the production setting.
  *   wide (1)             conservative FP32 four-wide walk of identity scenes (exact: wide.h)
@@ -387,6 +418,9 @@ int32_t rt_scene_get_option(const rt_scene* scene, const char* name, int64_t* va
  *   rebuild_depth_cap (42)    levels a rebuilt flattened instance tree may have (1 .. 42, the cap
  *                             that follows from the traversal stack; it can only be lowered): lets a
  *                             small scene exercise the depth guard of RT_COMMIT_REBUILD_FIT
+ *   rebuild_cluster_iter_cap (152)  iterations the clustered builder may take: the smaller of this
+ *                             and 4 ceil(log2 pairs) + 32 holds (152 is that cap at 2^30 pairs; it can
+ *                             only be lowered): lets a small scene exercise the fall-back to Morton
  * Used only by the parity tests that show the exactness proof has teeth. */
 int32_t rt_scene_set_unsafe_option(rt_scene* scene, const char* name, int64_t value);
 

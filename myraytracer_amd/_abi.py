@@ -109,6 +109,18 @@ class rt_rebuild_stats(C.Structure):
 
 REBUILD_SYMBOLS = ["rt_scene_commit_ex", "rt_scene_last_rebuild_stats"]
 
+# ---- the clustered builder, the detail record and the tree cost (appended under ABI 5: detected by symbol) ----
+RT_COMMIT_REBUILD_FIT_CLUSTERED = 8   # rt_scene_commit_ex flag, alone or with RT_COMMIT_REBUILD_FIT
+RT_BUILDER_NONE, RT_BUILDER_MORTON, RT_BUILDER_CLUSTERED = range(3)   # rt_rebuild_detail.builder
+
+
+class rt_rebuild_detail(C.Structure):
+    _fields_ = [("builder", C.c_int32), ("iterations", C.c_int32), ("fell_back", C.c_int32), ("pad", C.c_int32),
+                ("cluster_ms", C.c_double), ("cost_before", C.c_double), ("cost_after", C.c_double)]
+
+
+REBUILD_DETAIL_SYMBOLS = ["rt_scene_last_rebuild_detail", "rt_scene_fit_cost"]
+
 
 class rt_wide_dump(C.Structure):
     """rt_debug_wide_build / rt_debug_wide_read (rtcore.h): counts and scalars out, capacities in,
@@ -213,6 +225,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_mesh_vertex_count", "rt_scene_set_mesh_positions", "rt_scene_last_deform_stats",
     "rt_query_closest", "rt_query_occluded", "rt_query_stats", "rt_debug_query_tables",
     "rt_scene_commit_ex", "rt_scene_last_rebuild_stats",
+    *REBUILD_DETAIL_SYMBOLS,
 ]
 RT_ABI_VERSION = 5
 
@@ -331,6 +344,11 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.rt_scene_commit_ex.restype = C.c_int32
         lib.rt_scene_last_rebuild_stats.argtypes = [C.c_void_p, P(rt_rebuild_stats)]
         lib.rt_scene_last_rebuild_stats.restype = C.c_int32
+    if hasattr(lib, "rt_scene_fit_cost"):   # clustered rebuild, detail, tree cost (appended under ABI 5: detected by symbol)
+        lib.rt_scene_last_rebuild_detail.argtypes = [C.c_void_p, P(rt_rebuild_detail)]
+        lib.rt_scene_last_rebuild_detail.restype = C.c_int32
+        lib.rt_scene_fit_cost.argtypes = [C.c_void_p, c_double_p]
+        lib.rt_scene_fit_cost.restype = C.c_int32
     if hasattr(lib, "rt_query_closest"):   # ray queries (appended under ABI 5: detected by symbol)
         lib.rt_query_closest.argtypes = [C.c_void_p, C.c_int32, C.c_int64, P(rt_ray_batch), P(rt_hit_batch),
                                          P(rt_query_bounds), C.c_uint32, C.c_void_p]

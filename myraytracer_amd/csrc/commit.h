@@ -2,7 +2,7 @@
 // rtcore.h) and of what stages for them; the kernels are in refit.h, deform.h and rebuild.h.
 // Included into render.hip after the scene, replica and option types (one translation unit, like
 // query.h).  commit_impl is a short driver over the commit_* steps, which share one CommitPlan;
-// rebuild_fit is the RT_COMMIT_REBUILD_FIT step.  A commit runs under the scene lock with no render
+// rebuild_fit is the RT_COMMIT_REBUILD_FIT / RT_COMMIT_REBUILD_FIT_CLUSTERED step.  A commit runs under the scene lock with no render
 // in flight; its scratch lives in the replica's DevArrays, a rebuild's in one RebuildScratch.
 #pragma once
 
@@ -159,6 +159,7 @@ static int32_t last_stats(const rt_scene* s, Stats rt_scene::*which, Stats* out)
 }
 int32_t rt_scene_last_deform_stats(const rt_scene* s, rt_deform_stats* out) { return last_stats(s, &rt_scene::last_deform, out); }
 int32_t rt_scene_last_rebuild_stats(const rt_scene* s, rt_rebuild_stats* out) { return last_stats(s, &rt_scene::last_rebuild, out); }
+int32_t rt_scene_last_rebuild_detail(const rt_scene* s, rt_rebuild_detail* out) { return last_stats(s, &rt_scene::last_detail, out); }
 
 // ---- shared by the steps ------------------------------------------------------------------------------
 // World bounds of the moved triangle-mesh instances, on replica 0 (refit.h k_inst_bounds)
@@ -224,9 +225,13 @@ struct RebuildScratch {                           // RebuildScratch m{}: every p
     int32_t *left, *right, *parent, *leaf_parent, *cur, *next, *slots, *cnt, *off;
     W4Node* wn;
     char *sort_tmp, *scan_tmp;
+    // the clustered builder's (rebuild.h k_pc_*): two cluster arrays, neighbours, flag words and their scan
+    int32_t *cref[2], *nbr;
+    double* cbox[2];
+    unsigned long long *word, *wscan;
     // Points every part into the allocation at `at` and returns the bytes they take together
-    // (called with nullptr first, for the size)
-    size_t carve(char* at, int64_t n, int parts) {
+    // (called with nullptr first, for the size); nc = n for the clustered builder, else 0
+    size_t carve(char* at, int64_t n, int parts, int64_t nc) {
         size_t total = 0;
         auto take = [&](auto*& p, int64_t count) {
             p = reinterpret_cast<std::remove_reference_t<decltype(p)>>(reinterpret_cast<uintptr_t>(at) + total);
@@ -237,6 +242,8 @@ struct RebuildScratch {                           // RebuildScratch m{}: every p
         take(left, n); take(right, n); take(parent, n); take(leaf_parent, n);
         take(cur, n); take(next, n); take(slots, 4 * n); take(cnt, n + 1); take(off, n + 1);
         take(wn, n); take(sort_tmp, (int64_t)sort_bytes); take(scan_tmp, (int64_t)scan_bytes);
+        take(cref[0], nc); take(cref[1], nc); take(nbr, nc); take(cbox[0], 6 * nc); take(cbox[1], 6 * nc);
+        take(word, nc + 1); take(wscan, nc + 1);
         return total;
     }
     ~RebuildScratch() { (void)hipFree(base); }
@@ -247,7 +254,8 @@ struct RebuiltTree {                              // what one replica built
     std::vector<int64_t> level_count;             // nodes per level, root first
     int64_t nodes = 0;
     int32_t reason = RT_REBUILD_NONE;
-    double sort_ms = 0.0, build_ms = 0.0;
+    double sort_ms = 0.0, build_ms = 0.0, cluster_ms = 0.0;
+    int32_t iterations = 0, fell_back = 0;        // of the clustered builder
     void drop() { (void)hipFree(wnodes); (void)hipFree(levels); wnodes = nullptr; levels = nullptr; }
 };
 
@@ -284,7 +292,48 @@ static int32_t rebuild_collapse(const HostScene& S, DeviceReplica& r, int64_t de
     return RT_OK;
 }
 
-static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t depth_cap, RebuiltTree& R) {
+// The binary tree over the sorted pairs by clustering (rebuild.h k_pc_*): an iteration ends with one
+// synchronise and a four-byte read-back of the new cluster count, as a collapse level does.  false
+// in `built`: more than iter_cap iterations - the caller builds the Morton tree instead.
+static int32_t rebuild_cluster(DeviceReplica& r, int64_t n, int64_t iter_cap, RebuildScratch& m, RebuiltTree& R, bool& built) {
+    const auto t0 = CommitClock::now();
+    hipStream_t st = r.stream;
+    built = false;
+    hipLaunchKernelGGL(dev::k_pc_init, blocks_for(n), dim3(dev::kRbBlock), 0, st, (const uint32_t*)m.vals1, (const double*)m.pbox, n,
+                       m.cref[0], m.cbox[0]);
+    HIP_TRY(hipGetLastError());
+    int64_t count = n, next_id = n - 2;
+    int at = 0;
+    while (count > 1) {
+        if (R.iterations >= iter_cap) { R.cluster_ms = ms_since(t0); return RT_OK; }
+        const dim3 grid = blocks_for(count + 1), block(dev::kRbBlock);
+        hipLaunchKernelGGL(dev::k_pc_neighbour, grid, block, 0, st, (const double*)m.cbox[at], (int32_t)count, m.nbr);
+        hipLaunchKernelGGL(dev::k_pc_merge, grid, block, 0, st, (const int32_t*)m.nbr, (int32_t)count, m.word);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(m.scan_tmp, m.scan_bytes, m.word, m.wscan, (int)(count + 1), st));
+        dev::PcStep P{};
+        P.ref = m.cref[at]; P.box = m.cbox[at]; P.nbr = m.nbr; P.word = m.word; P.scan = m.wscan;
+        P.count = (int32_t)count; P.next_id = (int32_t)next_id; P.nodes = (int32_t)(n - 1);
+        P.oref = m.cref[at ^ 1]; P.obox = m.cbox[at ^ 1]; P.left = m.left; P.right = m.right; P.nbox = m.nbox;
+        hipLaunchKernelGGL(dev::k_pc_compact, grid, block, 0, st, P);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(st));
+        uint32_t alive = 0;                                  // the low half of the totals: the clusters left
+        HIP_TRY(hipMemcpy(&alive, m.wscan + count, sizeof(alive), hipMemcpyDeviceToHost));
+        if (alive < 1u || (int64_t)alive >= count) return fail(RT_ERR_DEVICE, "rebuild: a clustering iteration merged nothing");
+        next_id -= count - (int64_t)alive;
+        count = (int64_t)alive;
+        at ^= 1;
+        ++R.iterations;
+    }
+    if (next_id != -1) return fail(RT_ERR_DEVICE, "rebuild: the clustering did not end at the root");
+    R.cluster_ms = ms_since(t0);
+    built = true;
+    return RT_OK;
+}
+
+static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t depth_cap, bool clustered, int64_t iter_cap,
+                              RebuiltTree& R) {
     HIP_TRY(hipSetDevice(r.device));
     const auto t0 = CommitClock::now();
     const int64_t n = (int64_t)S.fpairs.size();
@@ -293,14 +342,19 @@ static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t dept
     RebuildScratch m{};                                      // null pointers: hipcub only says what it needs
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, m.sort_bytes, m.keys0, m.keys1, m.vals0, m.vals1, (int)n, 0, 63, st));
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, m.scan_bytes, m.cnt, m.off, (int)n, st));
-    const size_t total = m.carve(nullptr, n, parts);
+    if (clustered) {
+        size_t words = 0;
+        HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, words, m.word, m.wscan, (int)(n + 1), st));
+        m.scan_bytes = std::max(m.scan_bytes, words);
+    }
+    const size_t total = m.carve(nullptr, n, parts, clustered ? n : 0);
     if (hipMalloc((void**)&m.base, total) != hipSuccess) {
         (void)hipGetLastError();
         m.base = nullptr;
         R.reason = RT_REBUILD_NO_MEMORY;
         return RT_OK;
     }
-    m.carve(m.base, n, parts);
+    m.carve(m.base, n, parts, clustered ? n : 0);
     // 1. pair boxes and their union, Morton codes, the stable sort
     hipLaunchKernelGGL(dev::k_rb_pair_boxes, dim3((unsigned)parts), dim3(dev::kRbBlock), 0, st, (const DFitPair*)r.fpairs,
                        (const double*)r.lbox, (const DInstance*)r.insts, n, m.pbox, m.partial);
@@ -312,14 +366,22 @@ static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t dept
     HIP_TRY(hipStreamSynchronize(st));
     R.sort_ms = ms_since(t0);
     const auto t1 = CommitClock::now();
-    // 2. the binary radix tree and its boxes
-    dev::RbTree T{};
-    T.keys = m.keys1; T.n = (int32_t)n; T.left = m.left; T.right = m.right; T.parent = m.parent; T.leaf_parent = m.leaf_parent;
-    HIP_TRY(hipMemsetAsync(m.arrive, 0, (size_t)n * sizeof(unsigned), st));
-    hipLaunchKernelGGL(dev::k_rb_hierarchy, blocks_for(n - 1), dim3(dev::kRbBlock), 0, st, T);
-    hipLaunchKernelGGL(dev::k_rb_node_boxes, blocks_for(n), dim3(dev::kRbBlock), 0, st, T, (const uint32_t*)m.vals1,
-                       (const double*)m.pbox, m.arrive, m.nbox);
-    HIP_TRY(hipGetLastError());
+    // 2. the binary tree and its boxes: clustered, or the radix tree (also when the clustering gave up)
+    bool built = false;
+    if (clustered) {
+        const int32_t rc = rebuild_cluster(r, n, iter_cap, m, R, built);
+        if (rc != RT_OK) return rc;
+        R.fell_back = built ? 0 : 1;
+    }
+    if (!built) {
+        dev::RbTree T{};
+        T.keys = m.keys1; T.n = (int32_t)n; T.left = m.left; T.right = m.right; T.parent = m.parent; T.leaf_parent = m.leaf_parent;
+        HIP_TRY(hipMemsetAsync(m.arrive, 0, (size_t)n * sizeof(unsigned), st));
+        hipLaunchKernelGGL(dev::k_rb_hierarchy, blocks_for(n - 1), dim3(dev::kRbBlock), 0, st, T);
+        hipLaunchKernelGGL(dev::k_rb_node_boxes, blocks_for(n), dim3(dev::kRbBlock), 0, st, T, (const uint32_t*)m.vals1,
+                           (const double*)m.pbox, m.arrive, m.nbox);
+        HIP_TRY(hipGetLastError());
+    }
     // 3. four-wide nodes level by level
     const int32_t rc = rebuild_collapse(S, r, depth_cap, m, R);
     if (rc != RT_OK || R.reason != RT_REBUILD_NONE) return rc;
@@ -346,12 +408,42 @@ static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t dept
     return RT_OK;
 }
 
+// The cost of the fit tree replica r holds (rebuild.h k_fit_cost; rt_scene_fit_cost); 0 without one.
+// The partial sums go through the replica's bounds scratch: the scene lock is held.
+static int32_t fit_cost_on(const HostScene& S, DeviceReplica& r, double* cost) {
+    *cost = 0.0;
+    if (S.fit_root < 0 || S.fit_nodes <= 0 || S.wide_copy <= 0 || !r.wnodes) return RT_OK;
+    HIP_TRY(hipSetDevice(r.device));
+    if (!r.bounds_part.grow(dev::kFcBlocks + 1)) return fail(RT_ERR_DEVICE, "hipMalloc (tree cost scratch): out of memory");
+    const W4Node* fit = r.wnodes + S.fit_root;
+    hipLaunchKernelGGL(dev::k_fit_cost, dim3(dev::kFcBlocks), dim3(dev::kRbBlock), 0, r.stream, fit, S.fit_nodes, r.bounds_part.p);
+    hipLaunchKernelGGL(dev::k_fit_cost_fold, dim3(1), dim3(64), 0, r.stream, (const double*)r.bounds_part.p, dev::kFcBlocks, fit,
+                       r.bounds_part.p + dev::kFcBlocks);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(r.stream));
+    HIP_TRY(hipMemcpy(cost, r.bounds_part.p + dev::kFcBlocks, sizeof(double), hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+int32_t rt_scene_fit_cost(rt_scene* s, double* cost) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!cost) return fail(RT_ERR_INVALID_ARG, "cost is NULL");
+    *cost = 0.0;
+    if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
+    std::lock_guard<std::mutex> lock(s->mu);
+    if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
+    if (s->devs.empty() || s->host.winst.empty()) return RT_OK;
+    return fit_cost_on(s->host, s->devs[0], cost);
+}
+
 // The rebuild step of a commit (the scene lock is held, no render is in flight).  Returns RT_OK
 // also when nothing was rebuilt (s->last_rebuild says why); an error only for a device failure.
-static int32_t rebuild_fit(rt_scene* s) {
+// clustered: RT_COMMIT_REBUILD_FIT_CLUSTERED; s->last_detail says which builder made the tree.
+static int32_t rebuild_fit(rt_scene* s, bool clustered) {
     const auto t0 = CommitClock::now();
     HostScene& S = s->host;
     rt_rebuild_stats st{};
+    rt_rebuild_detail dt{};
     const bool has = S.fit_root >= 0 && S.wide_copy > 0 && !S.winst.empty();
     st.pairs = has ? (int64_t)S.fpairs.size() : 0;
     st.nodes_before = st.nodes_after = has ? S.fit_nodes : 0;
@@ -360,17 +452,27 @@ static int32_t rebuild_fit(rt_scene* s) {
         st.reason = reason;
         st.rebuilt = reason == RT_REBUILD_NONE ? 1 : 0;
         st.total_ms = ms_since(t0);
+        if (!st.rebuilt) { dt.builder = 0; dt.cost_after = dt.cost_before; }
         s->last_rebuild = st;
+        s->last_detail = dt;
         return (int32_t)RT_OK;
     };
     bool tree = has && S.fpairs.size() >= 2 && S.fpairs.size() < (size_t(1) << 30);
     for (const DeviceReplica& r : s->devs) tree = tree && r.wnodes && r.fpairs && r.lbox && r.insts;
     if (!tree) return done(RT_REBUILD_NO_TREE);
     if (S.dyn.fit_blocked) return done(RT_REBUILD_BLOCKED);
+    COMMIT_TRY(fit_cost_on(S, s->devs[0], &dt.cost_before));
+    // the clustering gives up after 4 ceil(log2 n) + 32 iterations (the test hook can only lower that)
+    int64_t log2n = 0;
+    while ((size_t(1) << log2n) < S.fpairs.size()) ++log2n;
+    const int64_t iter_cap = std::min<int64_t>(4 * log2n + 32, s->opt[kOptRebuildClusterIterCap]);
     try {
         std::vector<RebuiltTree> res(s->devs.size());
         for (size_t k = 0; k < res.size(); ++k) {
-            const int32_t rc = rebuild_fit_on(S, s->devs[k], s->opt[kOptRebuildDepthCap], res[k]);
+            const int32_t rc = rebuild_fit_on(S, s->devs[k], s->opt[kOptRebuildDepthCap], clustered, iter_cap, res[k]);
+            dt.iterations = std::max(dt.iterations, res[k].iterations);
+            dt.fell_back = std::max(dt.fell_back, res[k].fell_back);
+            dt.cluster_ms = std::max(dt.cluster_ms, res[k].cluster_ms);
             if (rc == RT_OK && res[k].reason == RT_REBUILD_NONE && res[k].level_count == res[0].level_count) continue;
             const int32_t reason = res[k].reason;
             for (size_t j = 0; j < res.size(); ++j) {
@@ -402,6 +504,8 @@ static int32_t rebuild_fit(rt_scene* s) {
         S.fit_depth = (int64_t)R0.level_count.size();
         st.nodes_after = S.fit_nodes;
         st.depth_after = S.fit_depth;
+        dt.builder = clustered && !dt.fell_back ? 2 : 1;
+        COMMIT_TRY(fit_cost_on(S, s->devs[0], &dt.cost_after));
         return done(RT_REBUILD_NONE);
     } catch (const std::bad_alloc&) {
         return fail(RT_ERR_OOM, "host allocation failed");
@@ -719,8 +823,9 @@ static int32_t commit_upload_and_refit(rt_scene* s, CommitPlan&) {
 static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) {
     if (stats) *stats = rt_commit_stats{};
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
-    if (flags & ~RT_COMMIT_REBUILD_FIT) return fail(RT_ERR_INVALID_ARG, "unknown commit flags");
-    const bool rebuild = (flags & RT_COMMIT_REBUILD_FIT) != 0;
+    if (flags & ~(RT_COMMIT_REBUILD_FIT | RT_COMMIT_REBUILD_FIT_CLUSTERED)) return fail(RT_ERR_INVALID_ARG, "unknown commit flags");
+    const bool clustered = (flags & RT_COMMIT_REBUILD_FIT_CLUSTERED) != 0;     // alone or with RT_COMMIT_REBUILD_FIT
+    const bool rebuild = clustered || (flags & RT_COMMIT_REBUILD_FIT) != 0;
     if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
     std::lock_guard<std::mutex> lock(s->mu);
     if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
@@ -729,10 +834,11 @@ static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) 
     if (s->staged.empty() && s->staged_deform.empty()) {
         int32_t rc = RT_OK;
         if (rebuild) {                                       // nothing staged: the pose as it stands
-            rc = rebuild_fit(s);
+            rc = rebuild_fit(s, clustered);
             if (rc == RT_OK) drop_tile_orders(s);
         } else {
             s->last_rebuild = rt_rebuild_stats{};
+            s->last_detail = rt_rebuild_detail{};
         }
         if (stats) stats->total_ms = ms_since(t0);
         return rc;
@@ -751,9 +857,10 @@ static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) 
         const double refit_ms = ms_since(t1);
         // on request the flattened instance tree again, from the pose just committed
         if (rebuild) {
-            COMMIT_TRY(rebuild_fit(s));
+            COMMIT_TRY(rebuild_fit(s, clustered));
         } else {
             s->last_rebuild = rt_rebuild_stats{};
+            s->last_detail = rt_rebuild_detail{};
         }
         if (stats) {
             stats->instances_moved = (int64_t)P.staged.size();

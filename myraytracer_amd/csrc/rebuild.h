@@ -31,6 +31,8 @@
 //       binary node's box, which equals the float union of the child node's slots (down and up are
 //       monotone); empty slots are +inf in all six rows with ref 0; pad is zero.
 // The octant copies are then written by refit.h k_octant_copies.  All stores are vector stores.
+// RT_COMMIT_REBUILD_FIT_CLUSTERED replaces k_rb_hierarchy + k_rb_node_boxes by the clustered builder
+// (k_pc_*, below); k_fit_cost is the tree cost of rt_scene_fit_cost.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
@@ -258,6 +260,171 @@ __global__ __launch_bounds__(kRbBlock) void k_rb_emit(RbLevel L) {
     for (int k = 0; k < 3; ++k) { n.pnear[k][c] = lo[k]; n.pfar[k][c] = hi[k]; }
     n.ref[c] = ref;
     n.pad[c] = 0;
+}
+
+// ---- the clustered builder (RT_COMMIT_REBUILD_FIT_CLUSTERED): parallel locally-ordered
+// clustering (Meister & Bittner 2018) over the Morton-sorted pairs.  It stands in for k_rb_hierarchy +
+// k_rb_node_boxes and fills what the collapse reads: left, right, nbox (binary node 0 the root) over
+// the same `sorted`.  The clusters live in two ping-pong arrays in Morton order: a ref (>= 0 a binary
+// node, < 0 the leaf ~sorted position) and an FP64 box.  An iteration is
+//   k_pc_neighbour  every cluster picks, among the kPcRadius clusters on either side, the one whose
+//       union box with it has the smallest surface area; equal areas go to the smaller i ^ j of the
+//       two positions.  For a fixed i that key is unique per j and the whole key is symmetric, so a
+//       pair of globally smallest key names each other: every iteration merges at least once.  Equal
+//       boxes pair up as (0, 1), (2, 3), ... - halving, not chaining.  (The boxes are finite, so no
+//       area is a NaN; an area compares the same whichever way round fmin / fmax saw a -0.0.)
+//   k_pc_merge      a cluster whose neighbour's neighbour is itself merges: the lower position lives
+//       on as the new binary node, the higher one dies; everyone else is copied.  One 64-bit word per
+//       cluster: alive in the low half, "creates a node" in the high half.
+//   an exclusive scan of the words (hipcub): new position in the low half, rank among the
+//       iteration's merges in the high half; entry `count` holds the totals.
+//   k_pc_compact    writes the next array and the new nodes.  Node ids are handed out downward from
+//       next_id (n - 2 at first), so the last merge is node 0.
+// Positions and ids come from the scan, never from a counter: every byte depends on the input only.
+// Kernel boundaries order everything; nothing is handed from block to block inside a kernel.
+constexpr int kPcRadius = 16;
+constexpr int kPcTile = kRbBlock + 2 * kPcRadius;
+
+__global__ __launch_bounds__(kRbBlock) void k_pc_init(const uint32_t* sorted, const double* pbox, int64_t n,
+                                                      int32_t* cref, double* cbox) {
+    const int64_t i = (int64_t)blockIdx.x * kRbBlock + threadIdx.x;
+    if (i >= n) return;
+    const double* b = pbox + 6 * (size_t)sorted[i];
+    cref[i] = ~(int32_t)i;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) cbox[6 * i + a] = b[a];
+}
+
+// The block's boxes and kPcRadius more on either side are staged in LDS, one row per component.
+__global__ __launch_bounds__(kRbBlock) void k_pc_neighbour(const double* cbox, int32_t count, int32_t* nbr) {
+    __shared__ double sm[6][kPcTile];
+    const int64_t first = (int64_t)blockIdx.x * kRbBlock - kPcRadius;
+    for (int e = threadIdx.x; e < 6 * kPcTile; e += kRbBlock) {
+        const int pos = e / 6, a = e - 6 * pos;
+        const int64_t g = first + pos;
+        sm[a][pos] = (g >= 0 && g < (int64_t)count) ? cbox[6 * g + a] : 0.0;
+    }
+    __syncthreads();
+    const int64_t i = first + kPcRadius + threadIdx.x;
+    if (i >= (int64_t)count) return;
+    double b[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) b[a] = sm[a][threadIdx.x + kPcRadius];
+    int32_t best = -1;
+    double bestA = 0.0;
+    uint32_t bestX = 0u;
+    for (int k = 0; k <= 2 * kPcRadius; ++k) {
+        const int64_t j = i - kPcRadius + k;
+        if (k == kPcRadius || j < 0 || j >= (int64_t)count) continue;
+        const int q = threadIdx.x + k;
+        const double dx = fmax(b[3], sm[3][q]) - fmin(b[0], sm[0][q]);
+        const double dy = fmax(b[4], sm[4][q]) - fmin(b[1], sm[1][q]);
+        const double dz = fmax(b[5], sm[5][q]) - fmin(b[2], sm[2][q]);
+        const double ar = dx * dy + dy * dz + dz * dx;
+        const uint32_t x = (uint32_t)(i ^ j);
+        if (best < 0 || ar < bestA || (ar == bestA && x < bestX)) { best = (int32_t)j; bestA = ar; bestX = x; }
+    }
+    nbr[i] = best;                                         // count >= 2: there is one
+}
+
+__global__ __launch_bounds__(kRbBlock) void k_pc_merge(const int32_t* nbr, int32_t count, unsigned long long* word) {
+    const int64_t i = (int64_t)blockIdx.x * kRbBlock + threadIdx.x;
+    if (i > (int64_t)count) return;
+    if (i == (int64_t)count) { word[i] = 0ull; return; }
+    const int32_t j = nbr[i];
+    const bool mutual = j >= 0 && j < count && nbr[j] == (int32_t)i;
+    word[i] = !mutual ? 1ull : ((int64_t)j > i ? (1ull << 32) | 1ull : 0ull);
+}
+
+struct PcStep {
+    const int32_t* ref;           // the clusters of this iteration
+    const double* box;
+    const int32_t* nbr;
+    const unsigned long long* word;
+    const unsigned long long* scan;   // exclusive scan of word
+    int32_t count;
+    int32_t next_id;              // the iteration's first merge becomes this binary node
+    int32_t nodes;                // binary nodes (n - 1): ids stay below
+    int32_t* oref;                // the clusters of the next one
+    double* obox;
+    int32_t* left;
+    int32_t* right;
+    double* nbox;
+};
+__global__ __launch_bounds__(kRbBlock) void k_pc_compact(PcStep P) {
+    const int64_t i = (int64_t)blockIdx.x * kRbBlock + threadIdx.x;
+    if (i >= (int64_t)P.count) return;
+    const unsigned long long w = P.word[i];
+    if (!(w & 1ull)) return;                               // merged into the position below
+    const unsigned long long s = P.scan[i];
+    const int64_t pos = (int64_t)(uint32_t)s;
+    if (pos >= (int64_t)P.count) return;
+    double b[6];
+#pragma unroll
+    for (int a = 0; a < 6; ++a) b[a] = P.box[6 * i + a];
+    int32_t ref = P.ref[i];
+    if (w >> 32) {
+        const int32_t j = P.nbr[i];
+        const int32_t id = P.next_id - (int32_t)(s >> 32);
+        if (id < 0 || id >= P.nodes || j < 0 || j >= P.count) return;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+            b[a] = fmin(b[a], P.box[6 * (size_t)j + a]);
+            b[3 + a] = fmax(b[3 + a], P.box[6 * (size_t)j + 3 + a]);
+        }
+        P.left[id] = ref;
+        P.right[id] = P.ref[j];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) P.nbox[6 * (size_t)id + a] = b[a];
+        ref = id;
+    }
+    P.oref[pos] = ref;
+#pragma unroll
+    for (int a = 0; a < 6; ++a) P.obox[6 * pos + a] = b[a];
+}
+
+// ---- the cost of a fit tree (rt_scene_fit_cost): the sum, over the non-empty slots of the nodes
+// given (octant copy 0's fit nodes, the root first), of the slot box's surface area ex ey + ey ez +
+// ez ex with the extents formed in FP64 from the float rows, over the same area of the union of the
+// root's slots.  A fixed grid, each block's sum in a fixed order (lanes by shuffle-xor 32 down to 1,
+// then the waves in order), then one wave folds the blocks' sums: the value depends on the tree only.
+constexpr int kFcBlocks = 64;
+__device__ __forceinline__ double wave_fsum(double v) { for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64); return v; }
+__global__ __launch_bounds__(kRbBlock) void k_fit_cost(const W4Node* nodes, int64_t count, double* partial) {
+    double sum = 0.0;
+    const int64_t stride = (int64_t)gridDim.x * kRbBlock;
+    for (int64_t t = (int64_t)blockIdx.x * kRbBlock + threadIdx.x; t < 4 * count; t += stride) {
+        const W4Node& n = nodes[t >> 2];
+        const int c = (int)(t & 3);
+        if (!(n.pnear[0][c] < HUGE_VALF)) continue;
+        const double ex = (double)n.pfar[0][c] - (double)n.pnear[0][c];
+        const double ey = (double)n.pfar[1][c] - (double)n.pnear[1][c];
+        const double ez = (double)n.pfar[2][c] - (double)n.pnear[2][c];
+        sum += ex * ey + ey * ez + ez * ex;
+    }
+    sum = wave_fsum(sum);
+    __shared__ double sm[kRbBlock / 64];
+    if ((threadIdx.x & 63) == 0) sm[threadIdx.x >> 6] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double v = sm[0];
+        for (int w = 1; w < kRbBlock / 64; ++w) v += sm[w];
+        partial[blockIdx.x] = v;
+    }
+}
+// One wave: partial[0 .. parts) folded, divided by the root's area -> out[0]
+__global__ __launch_bounds__(64) void k_fit_cost_fold(const double* partial, int parts, const W4Node* root, double* out) {
+    double sum = 0.0;
+    for (int p = threadIdx.x; p < parts; p += 64) sum += partial[p];
+    sum = wave_fsum(sum);
+    if (threadIdx.x != 0) return;
+    double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
+    for (int c = 0; c < 4; ++c) {
+        if (!(root->pnear[0][c] < HUGE_VALF)) continue;
+        for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], (double)root->pnear[a][c]); hi[a] = fmax(hi[a], (double)root->pfar[a][c]); }
+    }
+    const double rx = hi[0] - lo[0], ry = hi[1] - lo[1], rz = hi[2] - lo[2];
+    out[0] = sum / (rx * ry + ry * rz + rz * rx);
 }
 
 }  // namespace dev

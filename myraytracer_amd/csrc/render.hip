@@ -1355,7 +1355,7 @@ enum OptId {
     kOptQueue, kOptQueueLevels, kOptHitlog, kOptNodeshade, kOptLevels, kOptTreePpw, kOptFullFlights,
     kOptDeepCapMb, kOptBatches, kOptZerocopy, kOptSubmitEvents, kOptSubmitCounters, kOptSubmitDma,
     kOptDebugFailReplica, kOptWideDeltaScale, kOptNodeLists, kOptTileOrder, kOptFit, kOptQueueTail, kOptQueryBatch,
-    kOptRebuildDepthCap,
+    kOptRebuildDepthCap, kOptRebuildClusterIterCap,
     kOptCount
 };
 // `unsafe` options are test hooks: rt_scene_set_option refuses them (RT_ERR_INVALID_ARG); only the
@@ -1393,6 +1393,9 @@ static const OptDef kOptDefs[kOptCount] = {
     {"query_batch", 1 << 22, 64, 1 << 30},  // ray queries: rays per launch (and per staging pass of a host-array query)
     {"rebuild_depth_cap", (kStackCap - 2) / 3, 1, (kStackCap - 2) / 3, true},   // test hook: levels a rebuilt fit tree may have
                                                                                 // (rebuild_fit's depth guard on a small scene)
+    {"rebuild_cluster_iter_cap", 4 * 30 + 32, 1, 4 * 30 + 32, true},            // test hook: iterations the clustered builder may take
+                                                                                // (rebuild_fit takes the smaller of it and 4 ceil(log2 pairs) + 32;
+                                                                                // the default is that cap at 2^30 pairs, the most a tree holds)
 };
 
 struct rt_scene {
@@ -1425,6 +1428,7 @@ struct rt_scene {
     std::vector<StagedDeform> staged_deform;
     rt_deform_stats last_deform{};
     rt_rebuild_stats last_rebuild{};                  // of the last successful commit (rt_scene_commit_ex)
+    rt_rebuild_detail last_detail{};                  // ... and which builder made the tree (rt_scene_last_rebuild_detail)
 };
 
 static int64_t full_scratch_bytes(const FullScratch& f) {

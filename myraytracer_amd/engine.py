@@ -210,13 +210,19 @@ class RayTracerEngine:
         _check(load_library().rt_scene_set_camera(self._h, int(index), C.byref(cc)))
         self.scene.cameras[index] = camera
 
-    def commit(self, rebuild: bool = False) -> A.rt_commit_stats:
+    def commit(self, rebuild=False) -> A.rt_commit_stats:
         """Apply the staged transforms (rt_scene_commit): blocks until every replica is updated.
         With `rebuild` the flattened instance tree is then built again on the device for the new
-        pose (rt_scene_commit_ex, RT_COMMIT_REBUILD_FIT); last_rebuild_stats() says what happened."""
+        pose (rt_scene_commit_ex): True takes the Morton builder (RT_COMMIT_REBUILD_FIT),
+        "clustered" the clustered one (RT_COMMIT_REBUILD_FIT_CLUSTERED); last_rebuild_stats() and
+        last_rebuild_detail() say what happened."""
         st = A.rt_commit_stats()
         lib = load_library()
-        if rebuild:
+        if isinstance(rebuild, str):
+            if rebuild != "clustered":
+                raise ValueError('rebuild is False, True or "clustered"')
+            _check(lib.rt_scene_commit_ex(self._h, A.RT_COMMIT_REBUILD_FIT_CLUSTERED, C.byref(st)))
+        elif rebuild:
             _check(lib.rt_scene_commit_ex(self._h, A.RT_COMMIT_REBUILD_FIT, C.byref(st)))
         else:
             _check(lib.rt_scene_commit(self._h, C.byref(st)))
@@ -228,6 +234,21 @@ class RayTracerEngine:
         st = A.rt_rebuild_stats()
         _check(load_library().rt_scene_last_rebuild_stats(self._h, C.byref(st)))
         return st
+
+    def last_rebuild_detail(self) -> A.rt_rebuild_detail:
+        """Which builder made the tree of the last commit() (rt_scene_last_rebuild_detail): zeros
+        when it asked for no rebuild; builder 1 Morton, 2 clustered; the clustering's iterations and
+        time, whether it fell back to Morton, and the tree cost before and after."""
+        st = A.rt_rebuild_detail()
+        _check(load_library().rt_scene_last_rebuild_detail(self._h, C.byref(st)))
+        return st
+
+    def fit_cost(self) -> float:
+        """The cost of the flattened instance tree in use now (rt_scene_fit_cost): summed slot-box
+        surface areas over the root's; 0.0 when the scene has no such tree.  Lower is better."""
+        c = C.c_double(0.0)
+        _check(load_library().rt_scene_fit_cost(self._h, C.byref(c)))
+        return float(c.value)
 
     # -- deforming meshes (BVHBuilder.refit applied to a BLAS, BVH.swift:254-291)
     def vertex_count(self, object_index: int) -> int:

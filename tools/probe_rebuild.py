@@ -13,7 +13,10 @@ Reports (one JSON line, and the same as text):
                    every sphere by 1 % of its diameter first), host clock around the blocking call,
                    with the rt_rebuild_stats split (rb_sort_ms, rb_build_ms, rb_total_ms) and the tree's size
   create           rt_scene_create of the fresh scenes (build_ms + upload_ms of rt_scene_info)
-usage: probe_rebuild.py [--frames 200] [--commits 20] [--diameters 1,4,16]
+With --builder clustered the rebuilding commits take RT_COMMIT_REBUILD_FIT_CLUSTERED, and the rebuild rows
+and the rebuild_commit spread also carry cluster_ms, iterations, cost_before and cost_after
+(rt_rebuild_detail); --builder morton (the default) is the Morton builder and the output above.
+usage: probe_rebuild.py [--frames 200] [--commits 20] [--diameters 1,4,16] [--builder morton|clustered]
 The scene needs a GPU; nothing falls back."""
 import argparse
 import copy
@@ -38,6 +41,7 @@ p.add_argument("--frames", type=int, default=200)
 p.add_argument("--commits", type=int, default=20)
 p.add_argument("--diameters", default="1,4,16")
 p.add_argument("--scenes", default=os.path.join(ROOT, "scenes_cache"))
+p.add_argument("--builder", choices=("morton", "clustered"), default="morton")
 args = p.parse_args()
 
 
@@ -75,12 +79,21 @@ def spread(v):
 
 def rebuild_stats(eng):
     r = eng.last_rebuild_stats()
-    return {"rb_" + f: getattr(r, f) for f, _ in A.rt_rebuild_stats._fields_}
+    st = {"rb_" + f: getattr(r, f) for f, _ in A.rt_rebuild_stats._fields_}
+    if CLUSTERED:
+        d = eng.last_rebuild_detail()
+        assert d.builder == A.RT_BUILDER_CLUSTERED and not d.fell_back, "the clustered builder did not build the tree"
+        st.update({f: getattr(d, f) for f in DETAIL})
+    return st
 
 
+CLUSTERED = args.builder == "clustered"
+DETAIL = ("cluster_ms", "iterations", "cost_before", "cost_after")
 sc = scenes.scene_c3_instanced(path_dir=args.scenes)
 out = {"scene": "C3i", "lib_sha256_16": hashlib.sha256(open(M.engine.LIB_PATH, "rb").read()).hexdigest()[:16],
        "frames": args.frames}
+if CLUSTERED:
+    out["builder"] = args.builder
 dyn = M.RayTracerEngine(sc, dynamic=True)
 i0 = dyn.info()
 out["create_dynamic_ms"] = i0.build_ms + i0.upload_ms
@@ -104,7 +117,7 @@ def stage(diam, jitter=None):
 
 def timed_commit(rebuild):
     t0 = time.perf_counter()
-    st = dyn.commit(rebuild=rebuild)
+    st = dyn.commit(rebuild="clustered" if rebuild and CLUSTERED else rebuild)
     return {"wall_ms": (time.perf_counter() - t0) * 1e3, "total_ms": st.total_ms, "refit_ms": st.refit_ms}
 
 
@@ -146,7 +159,7 @@ for c in range(args.commits):
     r.update(rebuild_stats(dyn))
     reb.append(r)
 assert all(r["rb_rebuilt"] == 1 for r in reb), "a rebuilding commit did not rebuild"
-for key in ("wall_ms", "total_ms", "refit_ms", "rb_sort_ms", "rb_build_ms", "rb_total_ms"):
+for key in ("wall_ms", "total_ms", "refit_ms", "rb_sort_ms", "rb_build_ms", "rb_total_ms") + (DETAIL if CLUSTERED else ()):
     out["rebuild_commit_" + key] = spread([r[key] for r in reb])
 out["rebuild_tree"] = {k: reb[-1]["rb_" + k] for k in ("pairs", "nodes_before", "nodes_after", "depth_before", "depth_after")}
 dyn.close()
