@@ -198,6 +198,28 @@ public:
         check(rt_scene_fit_cost(scene_, &c));
         return c;
     }
+    /* Instance visibility (rtcore.h "instance visibility"): setVisible stages a flag for the instance
+     * of scene object `objectIndex` until commit(), which hides or shows it with the instance indices
+     * kept; isVisible is the flag as of the last commit; lastVisibilityStats() says what the last
+     * commit changed, whether it rebuilt the flattened instance tree on its own and whether the tree
+     * in use holds every visible pair. */
+    void setVisible(int32_t objectIndex, bool visible) {
+        const int32_t k = instanceOf(objectIndex);
+        if (k < 0) throw RenderError(RT_ERR_INVALID_ARG, "the object produced no instance");
+        check(rt_scene_set_instance_visible(scene_, k, visible ? 1 : 0));
+    }
+    bool isVisible(int32_t objectIndex) const {
+        const int32_t k = instanceOf(objectIndex);
+        if (k < 0) throw RenderError(RT_ERR_INVALID_ARG, "the object produced no instance");
+        int32_t v = 0;
+        check(rt_scene_instance_visible(scene_, k, &v));
+        return v != 0;
+    }
+    rt_visibility_stats lastVisibilityStats() const {
+        rt_visibility_stats st{};
+        check(rt_scene_last_visibility_stats(scene_, &st));
+        return st;
+    }
     /* Deforming meshes (an engine built with `deformable`, which implies `dynamic`): BVHBuilder.refit
      * (BVH.swift:254-291) applied to a BLAS on the device.  setPositions stages xyz triples (and, for a
      * mesh created with per-vertex normals, optionally new normals) for mesh object `objectIndex`

@@ -211,8 +211,10 @@ int32_t rt_scene_info_get(const rt_scene* scene, rt_scene_info* out);
  * RT_SCENE_DYNAMIC accepts new localToWorld matrices for its instances between renders;
  * rt_scene_commit then brings every acceleration structure up to date with the reference's refit
  * semantics: the TLAS keeps its topology and its bounds are recomputed bottom-up from the
- * instances' new world bounds.  No PLY is parsed again and no BLAS rebuilt.  Instances can not
- * be added or removed; vertices move only in a scene created with RT_SCENE_DEFORMABLE as well
+ * instances' new world bounds.  No PLY is parsed again and no BLAS rebuilt.  The instances a scene
+ * is created with can be hidden and shown again at a commit ("instance visibility" below), so a
+ * pool created up front spawns and despawns; instances that did not exist at rt_scene_create_ex
+ * can not be added.  Vertices move only in a scene created with RT_SCENE_DEFORMABLE as well
  * ("deforming meshes" below).  A dynamic scene always uses the transformed
  * layout (also while every matrix is the identity); scenes created without the flag behave
  * exactly as before.
@@ -353,7 +355,8 @@ int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);
  *       depends on the tree only.  RT_OK with cost 0 when the scene has no such tree;
  *       RT_ERR_UNSUPPORTED without RT_SCENE_DYNAMIC, RT_ERR_BUSY as rt_scene_commit.
  * Not rebuilt: the reference-form TLAS, the BLASes, the TLAS's four-wide marker tree (option fit = 0).
- * Instances can still not be added or removed. */
+ * A rebuild holds the pairs of the visible instances only ("instance visibility" below); instances
+ * that did not exist at rt_scene_create_ex can still not be added. */
 #define RT_COMMIT_REBUILD_FIT 1u
 #define RT_COMMIT_REBUILD_FIT_CLUSTERED 8u   /* rebuild with the clustered builder (bits 2 and 4 stay unknown) */
 #define RT_REBUILD_NONE        0    /* rt_rebuild_stats.reason: rebuilt, or no rebuild asked for */
@@ -384,6 +387,46 @@ typedef struct rt_rebuild_detail {
 } rt_rebuild_detail;
 int32_t rt_scene_last_rebuild_detail(const rt_scene* scene, rt_rebuild_detail* out);
 int32_t rt_scene_fit_cost(rt_scene* scene, double* cost);
+
+/* ---- instance visibility (appended under ABI 5; detect by symbol) -------------------------------
+ * Every instance of a scene created with RT_SCENE_DYNAMIC can be hidden and shown again at a commit;
+ * instance indices never change.  After the commit the scene behaves as the reference's refitTLAS()
+ * would on a context that holds only the visible instances, with the TLAS topology kept: a hidden
+ * instance is there for no ray (renders, shadow rays, bounces, queries) and counts towards no bound
+ * or constant (TLAS boxes, the scene's extent and centre, the pruning and widening constants, the
+ * conditioning check of the flattened instance tree).  With every instance hidden a frame is the
+ * one of a scene without objects and every query ray misses.  A hidden instance still takes staged
+ * transforms and deformations of its mesh: shown later it has the pose it would have had, and
+ * rt_scene_instance_bounds keeps reporting the box it has or would have.  What is NOT possible:
+ * instances (or meshes) that did not exist at rt_scene_create_ex, per-ray or per-render masks.
+ *   rt_scene_set_instance_visible   stages a flag (non-zero: visible) until the next commit, like
+ *       rt_scene_set_instance_transform: legal while renders are in flight, a second call for the
+ *       same instance replaces the first.  RT_ERR_UNSUPPORTED without RT_SCENE_DYNAMIC,
+ *       RT_ERR_INVALID_ARG (nothing staged) for a bad index.
+ *   rt_scene_set_instances_visible  the same for instances [first, first + count), one byte each;
+ *       RT_ERR_INVALID_ARG (nothing staged) for a range that is not inside the scene's instances.
+ *   rt_scene_instance_visible       the flag as of the last commit.
+ *   rt_scene_commit / _ex           apply staged visibility together with transforms and positions;
+ *       a commit with only visibility staged is a real commit.  A refused commit drops staged
+ *       visibility too and changes nothing.
+ * The flattened instance tree: a plain commit gives the slots of hidden pairs boxes no ray enters;
+ * a rebuilding commit builds the tree over the visible pairs only.  A commit that shows an instance
+ * the tree in use does not hold rebuilds the tree on its own (Morton builder unless the clustered
+ * flag is given; forced_rebuild = 1, rt_scene_last_rebuild_stats filled as for a requested rebuild).
+ * If that rebuild's guards trip the tree is incomplete (fit_complete = 0) and renders and queries
+ * walk the TLAS's marker tree, which always holds every instance, until a later rebuild succeeds. */
+int32_t rt_scene_set_instance_visible(rt_scene* scene, int32_t instance, int32_t visible);
+int32_t rt_scene_set_instances_visible(rt_scene* scene, int32_t first, int32_t count, const uint8_t* visible);
+int32_t rt_scene_instance_visible(const rt_scene* scene, int32_t instance, int32_t* visible);
+typedef struct rt_visibility_stats {
+    int64_t instances, visible;              /* after the commit                                    */
+    int64_t shown, hidden;                   /* changed by it                                       */
+    int64_t pairs, pairs_visible, pairs_in_tree;   /* (instance, leaf run) pairs: all, of visible
+                                                instances, held by the tree in use               */
+    int32_t forced_rebuild;                  /* 1: the commit rebuilt the tree on its own           */
+    int32_t fit_complete;                    /* 1: the tree in use holds every visible pair         */
+} rt_visibility_stats;
+int32_t rt_scene_last_visibility_stats(const rt_scene* scene, rt_visibility_stats* out);   /* of the last commit */
 
 /* Render options: tuning and test switches, each default being the production setting.
  *   wide (1)             conservative FP32 four-wide walk of identity scenes (exact: wide.h)

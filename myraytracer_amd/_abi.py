@@ -122,6 +122,17 @@ class rt_rebuild_detail(C.Structure):
 REBUILD_DETAIL_SYMBOLS = ["rt_scene_last_rebuild_detail", "rt_scene_fit_cost"]
 
 
+# ---- instance visibility (appended under ABI 5: detected by symbol) ----
+class rt_visibility_stats(C.Structure):
+    _fields_ = [("instances", C.c_int64), ("visible", C.c_int64), ("shown", C.c_int64), ("hidden", C.c_int64),
+                ("pairs", C.c_int64), ("pairs_visible", C.c_int64), ("pairs_in_tree", C.c_int64),
+                ("forced_rebuild", C.c_int32), ("fit_complete", C.c_int32)]
+
+
+VISIBILITY_SYMBOLS = ["rt_scene_set_instance_visible", "rt_scene_set_instances_visible", "rt_scene_instance_visible",
+                      "rt_scene_last_visibility_stats"]
+
+
 class rt_wide_dump(C.Structure):
     """rt_debug_wide_build / rt_debug_wide_read (rtcore.h): counts and scalars out, capacities in,
     caller-sized buffers."""
@@ -226,6 +237,7 @@ EXPORTED_SYMBOLS = [
     "rt_query_closest", "rt_query_occluded", "rt_query_stats", "rt_debug_query_tables",
     "rt_scene_commit_ex", "rt_scene_last_rebuild_stats",
     *REBUILD_DETAIL_SYMBOLS,
+    *VISIBILITY_SYMBOLS,
 ]
 RT_ABI_VERSION = 5
 
@@ -349,6 +361,15 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.rt_scene_last_rebuild_detail.restype = C.c_int32
         lib.rt_scene_fit_cost.argtypes = [C.c_void_p, c_double_p]
         lib.rt_scene_fit_cost.restype = C.c_int32
+    if hasattr(lib, "rt_scene_set_instance_visible"):   # instance visibility (appended under ABI 5: detected by symbol)
+        lib.rt_scene_set_instance_visible.argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        lib.rt_scene_set_instance_visible.restype = C.c_int32
+        lib.rt_scene_set_instances_visible.argtypes = [C.c_void_p, C.c_int32, C.c_int32, P(C.c_uint8)]
+        lib.rt_scene_set_instances_visible.restype = C.c_int32
+        lib.rt_scene_instance_visible.argtypes = [C.c_void_p, C.c_int32, c_int32_p]
+        lib.rt_scene_instance_visible.restype = C.c_int32
+        lib.rt_scene_last_visibility_stats.argtypes = [C.c_void_p, P(rt_visibility_stats)]
+        lib.rt_scene_last_visibility_stats.restype = C.c_int32
     if hasattr(lib, "rt_query_closest"):   # ray queries (appended under ABI 5: detected by symbol)
         lib.rt_query_closest.argtypes = [C.c_void_p, C.c_int32, C.c_int64, P(rt_ray_batch), P(rt_hit_batch),
                                          P(rt_query_bounds), C.c_uint32, C.c_void_p]

@@ -87,6 +87,64 @@ int32_t rt_scene_instance_bounds(const rt_scene* s, int32_t instance, double lo[
     return RT_OK;
 }
 
+// Instance visibility (rtcore.h "instance visibility"): staged like a transform, applied by a commit
+// visible: one byte per instance of [first, first + count), or null: `one` for all of them
+static int32_t stage_visible(rt_scene* s, int32_t first, int32_t count, const uint8_t* visible, int32_t one) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
+    const int64_t n = (int64_t)s->host.insts.size();
+    if (first < 0 || count < 0 || (int64_t)first + count > n) return fail(RT_ERR_INVALID_ARG, "bad instance index or range");
+    try {
+        std::lock_guard<std::mutex> lock(s->mu);
+        if (s->staged_vis.empty()) s->staged_vis.assign((size_t)n, -1);      // -1: nothing staged for the instance
+        for (int32_t k = 0; k < count; ++k) s->staged_vis[(size_t)(first + k)] = (int8_t)((visible ? visible[k] : one) ? 1 : 0);
+        return RT_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    }
+}
+int32_t rt_scene_set_instance_visible(rt_scene* s, int32_t instance, int32_t visible) {
+    return stage_visible(s, instance, 1, nullptr, visible ? 1 : 0);
+}
+int32_t rt_scene_set_instances_visible(rt_scene* s, int32_t first, int32_t count, const uint8_t* visible) {
+    if (s && s->host.dynamic && !visible) return fail(RT_ERR_INVALID_ARG, "visible is NULL");
+    return stage_visible(s, first, count, visible, 0);
+}
+int32_t rt_scene_instance_visible(const rt_scene* s, int32_t instance, int32_t* visible) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!visible) return fail(RT_ERR_INVALID_ARG, "visible is NULL");
+    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
+    if (instance < 0 || instance >= (int32_t)s->host.insts.size()) return fail(RT_ERR_INVALID_ARG, "bad instance index");
+    *visible = s->host.dyn.is_visible((size_t)instance) ? 1 : 0;
+    return RT_OK;
+}
+// The pairs of the flattened instance tree whose instance `flag` marks (null: all of them)
+static int64_t pairs_flagged(const HostScene& S, const std::vector<uint8_t>* flag) {
+    if (!flag || flag->empty()) return (int64_t)S.fpairs.size();
+    int64_t c = 0;
+    for (const DFitPair& p : S.fpairs) c += (*flag)[(size_t)p.inst] ? 1 : 0;
+    return c;
+}
+static bool has_fit_tree(const HostScene& S) { return S.fit_root >= 0 && S.wide_copy > 0 && !S.winst.empty(); }
+// The counts as the host holds them now (they change at a commit only); shown, hidden and
+// forced_rebuild are the last commit's
+int32_t rt_scene_last_visibility_stats(const rt_scene* s, rt_visibility_stats* out) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
+    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
+    const HostScene& S = s->host;
+    rt_visibility_stats v = s->last_vis;
+    v.instances = (int64_t)S.insts.size();
+    v.visible = S.dynamic ? S.dyn.n_visible : v.instances;
+    const bool tree = has_fit_tree(S);
+    v.pairs = tree ? (int64_t)S.fpairs.size() : 0;
+    v.pairs_visible = tree ? pairs_flagged(S, &S.dyn.visible) : 0;
+    v.pairs_in_tree = tree ? pairs_flagged(S, &S.dyn.in_tree) : 0;
+    v.fit_complete = tree && !S.dyn.fit_incomplete ? 1 : 0;
+    *out = v;
+    return RT_OK;
+}
+
 // The BLAS an RT_OBJ_MESH object produced, through the retained object -> BLAS map (a mesh whose id
 // a MeshInstance took over has no instance of its own, but its BLAS is still used); -1: none
 static int32_t deform_blas_of(const rt_scene* s, int32_t object_index) {
@@ -256,13 +314,15 @@ struct RebuiltTree {                              // what one replica built
     int32_t reason = RT_REBUILD_NONE;
     double sort_ms = 0.0, build_ms = 0.0, cluster_ms = 0.0;
     int32_t iterations = 0, fell_back = 0;        // of the clustered builder
+    const int32_t* live = nullptr;                // while it is built: live pair -> pair (null: the same)
     void drop() { (void)hipFree(wnodes); (void)hipFree(levels); wnodes = nullptr; levels = nullptr; }
 };
 
 // Four-wide nodes from the binary tree, a level per pass: the level's nodes are wn[base, base + count).
 // A guard that trips sets R.reason.
-static int32_t rebuild_collapse(const HostScene& S, DeviceReplica& r, int64_t depth_cap, RebuildScratch& m, RebuiltTree& R) {
-    const int64_t n = (int64_t)S.fpairs.size(), n_main = S.fit_root;
+static int32_t rebuild_collapse(const HostScene& S, DeviceReplica& r, int64_t n, int64_t depth_cap, RebuildScratch& m,
+                                RebuiltTree& R) {
+    const int64_t n_main = S.fit_root;
     hipStream_t st = r.stream;
     HIP_TRY(hipMemsetAsync(m.cur, 0, sizeof(int32_t), st));                 // the root: binary node 0
     int64_t base = 0, count = 1;
@@ -271,7 +331,7 @@ static int32_t rebuild_collapse(const HostScene& S, DeviceReplica& r, int64_t de
         if (8 * (size_t)(n_main + base + count) * sizeof(W4Node) >= (size_t(1) << 32)) { R.reason = RT_REBUILD_TOO_LARGE; return RT_OK; }
         if (base + count > n - 1) return fail(RT_ERR_DEVICE, "rebuild: more four-wide nodes than binary nodes");
         dev::RbLevel L{};
-        L.left = m.left; L.right = m.right; L.nbox = m.nbox; L.pbox = m.pbox; L.sorted = m.vals1; L.cur = m.cur;
+        L.left = m.left; L.right = m.right; L.nbox = m.nbox; L.pbox = m.pbox; L.sorted = m.vals1; L.live = R.live; L.cur = m.cur;
         L.count = (int32_t)count; L.slots = m.slots; L.cnt = m.cnt; L.off = m.off; L.next = m.next; L.nodes = m.wn + base;
         L.child_base = (int32_t)(n_main + base + count);
         hipLaunchKernelGGL(dev::k_rb_collapse, blocks_for(count + 1), dim3(dev::kRbBlock), 0, st, L);
@@ -332,12 +392,58 @@ static int32_t rebuild_cluster(DeviceReplica& r, int64_t n, int64_t iter_cap, Re
     return RT_OK;
 }
 
+// The live pairs of one replica in ascending order (rebuild.h k_rb_live_*): flags, their exclusive
+// scan, the scatter.  One allocation, freed with the struct; live stays null when it failed.
+struct LivePairs {
+    char* base = nullptr;
+    int32_t* live = nullptr;
+    ~LivePairs() { (void)hipFree(base); }
+};
+static int32_t rebuild_live_pairs(const HostScene& S, DeviceReplica& r, int64_t n_live, LivePairs& lp, RebuiltTree& R) {
+    const int64_t n_all = (int64_t)S.fpairs.size();
+    hipStream_t st = r.stream;
+    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
+    size_t scan_bytes = 0;
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (int)(n_all + 1), st));
+    const size_t words = pad((size_t)(n_all + 1) * sizeof(int32_t));
+    if (hipMalloc((void**)&lp.base, 3 * words + pad(scan_bytes)) != hipSuccess) {
+        (void)hipGetLastError();
+        lp.base = nullptr;
+        R.reason = RT_REBUILD_NO_MEMORY;
+        return RT_OK;
+    }
+    int32_t* flag = (int32_t*)lp.base;
+    int32_t* place = (int32_t*)(lp.base + words);
+    int32_t* live = (int32_t*)(lp.base + 2 * words);
+    hipLaunchKernelGGL(dev::k_rb_live_flags, blocks_for(n_all + 1), dim3(dev::kRbBlock), 0, st, (const DFitPair*)r.fpairs,
+                       (const DInstance*)r.insts, n_all, flag);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipcub::DeviceScan::ExclusiveSum(lp.base + 3 * words, scan_bytes, flag, place, (int)(n_all + 1), st));
+    hipLaunchKernelGGL(dev::k_rb_live_scatter, blocks_for(n_all), dim3(dev::kRbBlock), 0, st, (const int32_t*)flag,
+                       (const int32_t*)place, n_all, n_live, live);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(st));
+    int32_t total = -1;
+    HIP_TRY(hipMemcpy(&total, place + n_all, sizeof(total), hipMemcpyDeviceToHost));
+    if ((int64_t)total != n_live) return fail(RT_ERR_DEVICE, "rebuild: the device and the host count different live pairs");
+    lp.live = live;
+    return RT_OK;
+}
+
+// n_live: the pairs of the visible instances (the host's count); fewer than all of them: the tree is
+// built over those alone
 static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t depth_cap, bool clustered, int64_t iter_cap,
-                              RebuiltTree& R) {
+                              int64_t n_live, RebuiltTree& R) {
     HIP_TRY(hipSetDevice(r.device));
     const auto t0 = CommitClock::now();
-    const int64_t n = (int64_t)S.fpairs.size();
+    const int64_t n = n_live;
     hipStream_t st = r.stream;
+    LivePairs lp;
+    if (n_live < (int64_t)S.fpairs.size()) {
+        const int32_t rc = rebuild_live_pairs(S, r, n_live, lp, R);
+        if (rc != RT_OK || R.reason != RT_REBUILD_NONE) return rc;
+    }
+    R.live = lp.live;
     const int parts = (int)std::min<int64_t>(dev::kRbParts, (n + dev::kRbBlock - 1) / dev::kRbBlock);
     RebuildScratch m{};                                      // null pointers: hipcub only says what it needs
     HIP_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, m.sort_bytes, m.keys0, m.keys1, m.vals0, m.vals1, (int)n, 0, 63, st));
@@ -357,7 +463,7 @@ static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t dept
     m.carve(m.base, n, parts, clustered ? n : 0);
     // 1. pair boxes and their union, Morton codes, the stable sort
     hipLaunchKernelGGL(dev::k_rb_pair_boxes, dim3((unsigned)parts), dim3(dev::kRbBlock), 0, st, (const DFitPair*)r.fpairs,
-                       (const double*)r.lbox, (const DInstance*)r.insts, n, m.pbox, m.partial);
+                       (const double*)r.lbox, (const DInstance*)r.insts, (const int32_t*)lp.live, n, m.pbox, m.partial);
     hipLaunchKernelGGL(dev::k_fold_boxes, dim3(1), dim3(64), 0, st, (const double*)m.partial, parts, m.ubox);
     hipLaunchKernelGGL(dev::k_rb_morton, blocks_for(n), dim3(dev::kRbBlock), 0, st, (const double*)m.pbox, (const double*)m.ubox, n,
                        m.keys0, m.vals0);
@@ -383,7 +489,7 @@ static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t dept
         HIP_TRY(hipGetLastError());
     }
     // 3. four-wide nodes level by level
-    const int32_t rc = rebuild_collapse(S, r, depth_cap, m, R);
+    const int32_t rc = rebuild_collapse(S, r, n, depth_cap, m, R);
     if (rc != RT_OK || R.reason != RT_REBUILD_NONE) return rc;
     // 4. the new node array: the eight main parts as they are, the new fit nodes behind copy 0's,
     //    then their octant copies (over the level list, deepest level first)
@@ -444,7 +550,8 @@ static int32_t rebuild_fit(rt_scene* s, bool clustered) {
     HostScene& S = s->host;
     rt_rebuild_stats st{};
     rt_rebuild_detail dt{};
-    const bool has = S.fit_root >= 0 && S.wide_copy > 0 && !S.winst.empty();
+    const bool has = has_fit_tree(S);
+    const int64_t n_live = has ? pairs_flagged(S, &S.dyn.visible) : 0;     // the tree holds the visible pairs only
     st.pairs = has ? (int64_t)S.fpairs.size() : 0;
     st.nodes_before = st.nodes_after = has ? S.fit_nodes : 0;
     st.depth_before = st.depth_after = has ? S.fit_depth : 0;
@@ -457,19 +564,19 @@ static int32_t rebuild_fit(rt_scene* s, bool clustered) {
         s->last_detail = dt;
         return (int32_t)RT_OK;
     };
-    bool tree = has && S.fpairs.size() >= 2 && S.fpairs.size() < (size_t(1) << 30);
+    bool tree = has && n_live >= 2 && S.fpairs.size() < (size_t(1) << 30);
     for (const DeviceReplica& r : s->devs) tree = tree && r.wnodes && r.fpairs && r.lbox && r.insts;
     if (!tree) return done(RT_REBUILD_NO_TREE);
     if (S.dyn.fit_blocked) return done(RT_REBUILD_BLOCKED);
     COMMIT_TRY(fit_cost_on(S, s->devs[0], &dt.cost_before));
     // the clustering gives up after 4 ceil(log2 n) + 32 iterations (the test hook can only lower that)
     int64_t log2n = 0;
-    while ((size_t(1) << log2n) < S.fpairs.size()) ++log2n;
+    while ((int64_t(1) << log2n) < n_live) ++log2n;
     const int64_t iter_cap = std::min<int64_t>(4 * log2n + 32, s->opt[kOptRebuildClusterIterCap]);
     try {
         std::vector<RebuiltTree> res(s->devs.size());
         for (size_t k = 0; k < res.size(); ++k) {
-            const int32_t rc = rebuild_fit_on(S, s->devs[k], s->opt[kOptRebuildDepthCap], clustered, iter_cap, res[k]);
+            const int32_t rc = rebuild_fit_on(S, s->devs[k], s->opt[kOptRebuildDepthCap], clustered, iter_cap, n_live, res[k]);
             dt.iterations = std::max(dt.iterations, res[k].iterations);
             dt.fell_back = std::max(dt.fell_back, res[k].fell_back);
             dt.cluster_ms = std::max(dt.cluster_ms, res[k].cluster_ms);
@@ -502,6 +609,8 @@ static int32_t rebuild_fit(rt_scene* s, bool clustered) {
         S.wide_copy = S.fit_root + R0.nodes;
         S.fit_nodes = R0.nodes;
         S.fit_depth = (int64_t)R0.level_count.size();
+        S.dyn.in_tree = S.dyn.visible;                      // the pairs the new tree holds
+        S.dyn.fit_incomplete = false;
         st.nodes_after = S.fit_nodes;
         st.depth_after = S.fit_depth;
         dt.builder = clustered && !dt.fell_back ? 2 : 1;
@@ -518,6 +627,7 @@ static int32_t rebuild_fit(rt_scene* s, bool clustered) {
 struct CommitPlan {
     std::vector<std::pair<int32_t, std::array<double, 16>>> staged;   // (instance, new localToWorld)
     std::vector<rt_scene::StagedDeform> sdef;
+    std::vector<int8_t> svis;                     // per instance: -1 nothing staged, else the new flag (or empty)
     std::vector<char> deformed;                   // per BLAS: new positions are staged for it
     // per staged deformation: its host arrays in a replica's def_stage, its first |e1||e2| partial in def_part
     std::vector<int64_t> pos_off, nrm_off, part_off;
@@ -528,6 +638,7 @@ struct CommitPlan {
     std::vector<int32_t> rebound;                 // the instances of the deformed meshes ...
     std::vector<double> rebound_box;              // ... and their new world bounds
     rt_deform_stats dst{};
+    rt_visibility_stats vst{};
     double bounds_ms = 0.0;
     CommitClock::time_point t0;
 
@@ -535,6 +646,7 @@ struct CommitPlan {
         const HostScene& S = s->host;
         staged.swap(s->staged);
         sdef.swap(s->staged_deform);
+        svis.swap(s->staged_vis);
         deformed.assign(S.dyn.blas.size(), 0);
         later.assign(staged.size(), 0);
         nb.assign(6 * staged.size(), 0.0);
@@ -786,6 +898,21 @@ static int32_t commit_rebound_deformed(rt_scene* s, CommitPlan& P) {
 
 // Host: DInstance, instance bounds, then TLAS bounds bottom-up, TLAS records, tbox and the margins'
 // constants (scene.cpp refit_host_scene)
+// The staged visibility flags become the scene's: from here on refit_host_scene leaves the hidden
+// instances out, and the upload gives their device DInstance a root box of NaNs.  Nothing here can
+// un-hide: a hidden instance's host DInstance keeps (and commit_rebound_deformed rewrites) its real box.
+static int32_t commit_apply_visibility(rt_scene* s, CommitPlan& P) {
+    DynScene& Y = s->host.dyn;
+    for (size_t i = 0; i < P.svis.size() && i < Y.visible.size(); ++i) {
+        if (P.svis[i] < 0 || (P.svis[i] != 0) == (Y.visible[i] != 0)) continue;
+        Y.visible[i] = P.svis[i] ? 1 : 0;
+        ++(P.svis[i] ? P.vst.shown : P.vst.hidden);
+    }
+    Y.n_visible = 0;
+    for (const uint8_t v : Y.visible) Y.n_visible += v ? 1 : 0;
+    return RT_OK;
+}
+
 static int32_t commit_host_refit(rt_scene* s, CommitPlan& P) {
     HostScene& S = s->host;
     for (size_t q = 0; q < P.staged.size(); ++q) {
@@ -803,9 +930,22 @@ static int32_t commit_host_refit(rt_scene* s, CommitPlan& P) {
 static int32_t commit_upload_and_refit(rt_scene* s, CommitPlan&) {
     const HostScene& S = s->host;
     const DynScene& Y = S.dyn;
+    // The device copy of a hidden instance has a BLAS root box of NaNs.  Every walk accepts a
+    // primitive of instance k only after the FP64 slab test of k's root box with the local ray
+    // (device.h, wide.h); every plane distance of a NaN box is a NaN, so tmax is one and the test
+    // fails in both of slab_hit's forms: no kernel changes.  The host keeps the real box.
+    std::vector<DInstance> masked;
+    const std::vector<DInstance>* dinsts = &S.insts;
+    if (Y.n_visible < (int64_t)S.insts.size()) {
+        masked = S.insts;
+        for (size_t i = 0; i < masked.size(); ++i)
+            if (!Y.is_visible(i))
+                for (int a = 0; a < 3; ++a) masked[i].root_lo[a] = masked[i].root_hi[a] = std::numeric_limits<double>::quiet_NaN();
+        dinsts = &masked;
+    }
     for (DeviceReplica& r : s->devs) {
         HIP_TRY(hipSetDevice(r.device));
-        HIP_TRY(hipMemcpy(r.insts, S.insts.data(), S.insts.size() * sizeof(DInstance), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(r.insts, dinsts->data(), dinsts->size() * sizeof(DInstance), hipMemcpyHostToDevice));
         if (!Y.tlas_recs.empty())
             HIP_TRY(hipMemcpy(r.recs + S.blas_records, Y.tlas_recs.data(), Y.tlas_recs.size() * sizeof(WRec),
                               hipMemcpyHostToDevice));
@@ -831,7 +971,8 @@ static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) 
     if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
     const auto t0 = CommitClock::now();
     s->last_deform = rt_deform_stats{};
-    if (s->staged.empty() && s->staged_deform.empty()) {
+    if (s->staged.empty() && s->staged_deform.empty() && s->staged_vis.empty()) {
+        s->last_vis = rt_visibility_stats{};
         int32_t rc = RT_OK;
         if (rebuild) {                                       // nothing staged: the pose as it stands
             rc = rebuild_fit(s, clustered);
@@ -851,13 +992,21 @@ static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) 
             COMMIT_TRY(step(s, P));
         // the transforms: the host's structures, then every replica's
         const auto t1 = CommitClock::now();
-        for (auto step : {commit_host_refit, commit_upload_and_refit}) COMMIT_TRY(step(s, P));
+        for (auto step : {commit_apply_visibility, commit_host_refit, commit_upload_and_refit}) COMMIT_TRY(step(s, P));
         drop_tile_orders(s);
         s->last_deform = P.dst;
+        s->last_vis = P.vst;
         const double refit_ms = ms_since(t1);
+        // a walk must never use a tree that lacks a visible pair: the commit that shows an instance
+        // the tree does not hold rebuilds it on its own; until a rebuild succeeds the walks take tw_walk
+        DynScene& Y = s->host.dyn;
+        bool complete = true;
+        for (size_t i = 0; i < Y.visible.size() && has_fit_tree(s->host); ++i) complete = complete && (!Y.visible[i] || Y.in_tree[i]);
+        Y.fit_incomplete = !complete;
         // on request the flattened instance tree again, from the pose just committed
-        if (rebuild) {
+        if (rebuild || !complete) {
             COMMIT_TRY(rebuild_fit(s, clustered));
+            s->last_vis.forced_rebuild = (!rebuild && s->last_rebuild.rebuilt) ? 1 : 0;
         } else {
             s->last_rebuild = rt_rebuild_stats{};
             s->last_detail = rt_rebuild_detail{};

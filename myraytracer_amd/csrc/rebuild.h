@@ -50,15 +50,39 @@ constexpr int kRbParts = 1024;            // blocks of k_rb_pair_boxes at the mo
 constexpr int kRbMaxClimb = 128;          // a radix tree over 63 + 32 prefix bits is shallower
 constexpr int32_t kRbEmpty = INT32_MIN;   // an empty slot of k_rb_collapse (pairs stay below 2^30)
 
-// Grid-stride over the pairs: pbox[6 p] and one partial union per block (partial[6 * blockIdx.x]).
+// ---- the live pairs (rtcore.h "instance visibility"): a rebuild holds the pairs of the visible
+// instances only.  A pair is live when the device copy of its instance's DInstance has a root box
+// (a hidden one has NaNs there, commit.h).  k_rb_live_flags writes the flags (n + 1 entries, the last
+// 0), an exclusive scan (hipcub) gives every live pair its place and, in entry n, their number, and
+// k_rb_live_scatter writes live[place] = pair: ascending pair order, from the input only.  The
+// builder then works on the n_live compact indices i; only k_rb_pair_boxes (pair live[i]) and
+// k_rb_emit (terminal slot ~live[i]) translate.  With every instance visible the host passes
+// live == nullptr: i is the pair, and every byte is what it was before visibility.
+__global__ __launch_bounds__(kRbBlock) void k_rb_live_flags(const DFitPair* fpairs, const DInstance* insts, int64_t n,
+                                                            int32_t* flag) {
+    const int64_t p = (int64_t)blockIdx.x * kRbBlock + threadIdx.x;
+    if (p > n) return;
+    if (p == n) { flag[p] = 0; return; }
+    const double r = insts[fpairs[p].inst].root_lo[0];
+    flag[p] = r == r ? 1 : 0;
+}
+__global__ __launch_bounds__(kRbBlock) void k_rb_live_scatter(const int32_t* flag, const int32_t* place, int64_t n,
+                                                              int64_t n_live, int32_t* live) {
+    const int64_t p = (int64_t)blockIdx.x * kRbBlock + threadIdx.x;
+    if (p >= n || !flag[p]) return;
+    const int64_t at = place[p];
+    if (at >= 0 && at < n_live) live[at] = (int32_t)p;     // n_live is the host's count: never past the array
+}
+
+// Grid-stride over the (live) pairs: pbox[6 i] and one partial union per block (partial[6 * blockIdx.x]).
 __global__ __launch_bounds__(kRbBlock) void k_rb_pair_boxes(const DFitPair* fpairs, const double* lbox,
-                                                            const DInstance* insts, int64_t n, double* pbox,
-                                                            double* partial) {
+                                                            const DInstance* insts, const int32_t* live, int64_t n,
+                                                            double* pbox, double* partial) {
     double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
     const int64_t stride = (int64_t)gridDim.x * kRbBlock;
     for (int64_t p = (int64_t)blockIdx.x * kRbBlock + threadIdx.x; p < n; p += stride) {
         double wlo[3], whi[3];
-        pair_world_box(fpairs[p], lbox, insts, wlo, whi);
+        pair_world_box(fpairs[live ? live[p] : p], lbox, insts, wlo, whi);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             pbox[6 * p + k] = wlo[k]; pbox[6 * p + 3 + k] = whi[k];
@@ -187,8 +211,9 @@ struct RbLevel {
     const int32_t* left;
     const int32_t* right;
     const double* nbox;           // per binary internal node
-    const double* pbox;           // per pair
-    const uint32_t* sorted;       // sorted position -> pair
+    const double* pbox;           // per (live) pair
+    const uint32_t* sorted;       // sorted position -> (live) pair
+    const int32_t* live;          // live pair -> pair (null: the same)
     const int32_t* cur;           // the level's binary roots
     int32_t count;                // nodes of the level
     int32_t* slots;               // 4 per node: a binary ref or kRbEmpty
@@ -246,7 +271,7 @@ __global__ __launch_bounds__(kRbBlock) void k_rb_emit(RbLevel L) {
         if (s < 0) {
             const uint32_t p = L.sorted[~s];
             b = L.pbox + 6 * (size_t)p;
-            ref = ~(int32_t)p;
+            ref = ~(L.live ? L.live[p] : (int32_t)p);
         } else {
             int rank = 0;
             for (int k = 0; k < c; ++k) rank += L.slots[4 * i + k] >= 0 ? 1 : 0;
@@ -396,7 +421,7 @@ __global__ __launch_bounds__(kRbBlock) void k_fit_cost(const W4Node* nodes, int6
     for (int64_t t = (int64_t)blockIdx.x * kRbBlock + threadIdx.x; t < 4 * count; t += stride) {
         const W4Node& n = nodes[t >> 2];
         const int c = (int)(t & 3);
-        if (!(n.pnear[0][c] < HUGE_VALF)) continue;
+        if (!(n.pnear[0][c] < HUGE_VALF) || refit_slot_hidden(n, c)) continue;   // empty, or nothing visible below
         const double ex = (double)n.pfar[0][c] - (double)n.pnear[0][c];
         const double ey = (double)n.pfar[1][c] - (double)n.pnear[1][c];
         const double ez = (double)n.pfar[2][c] - (double)n.pnear[2][c];
@@ -420,7 +445,7 @@ __global__ __launch_bounds__(64) void k_fit_cost_fold(const double* partial, int
     if (threadIdx.x != 0) return;
     double lo[3] = {HUGE_VAL, HUGE_VAL, HUGE_VAL}, hi[3] = {-HUGE_VAL, -HUGE_VAL, -HUGE_VAL};
     for (int c = 0; c < 4; ++c) {
-        if (!(root->pnear[0][c] < HUGE_VALF)) continue;
+        if (!(root->pnear[0][c] < HUGE_VALF) || refit_slot_hidden(*root, c)) continue;
         for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], (double)root->pnear[a][c]); hi[a] = fmax(hi[a], (double)root->pfar[a][c]); }
     }
     const double rx = hi[0] - lo[0], ry = hi[1] - lo[1], rz = hi[2] - lo[2];

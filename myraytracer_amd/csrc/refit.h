@@ -15,7 +15,7 @@
 //       TreeSlotBox the TLAS's instance markers their TLAS leaf box (DWideInst::tbox) and the
 //       flattened instance tree's pairs pair_world_box; by LeafRunBox a deformed BLAS's leaf runs
 //       their lbox (deform.h) - an inner slot takes the union of its child node's slots; empty
-//       slots stay +inf.  Works on octant copy 0, whose slots are in sorted order: a child is found
+//       slots stay +inf; the slot of a hidden instance takes the hidden encoding (kHiddenNear).  Works on octant copy 0, whose slots are in sorted order: a child is found
 //       by its ref, and a union does not depend on the order.
 //   k_octant_copies  the eight octant copies of the refit nodes again (scene.cpp
 //       wide_octant_copies' rule: near / far rows per octant, slots stable-sorted by centre
@@ -198,22 +198,42 @@ struct TreeSlotBox {
     const DFitPair* fpairs;
     const double* lbox;
     const DInstance* insts;
-    __device__ __forceinline__ void operator()(int32_t ref, double lo[3], double hi[3]) const {
+    // false: the slot's instance is hidden (rtcore.h "instance visibility") - the host gave its
+    // marker a tbox of NaNs and the device copy of its DInstance a root box of NaNs (commit.h)
+    __device__ __forceinline__ bool operator()(int32_t ref, double lo[3], double hi[3]) const {
         if (marker_base >= 0) {
             const double* b = winst[~ref - marker_base].tbox;
             for (int k = 0; k < 3; ++k) { lo[k] = b[k]; hi[k] = b[3 + k]; }
-        } else {
-            pair_world_box(fpairs[~ref], lbox, insts, lo, hi);
+            return b[0] == b[0];
         }
+        const DFitPair p = fpairs[~ref];
+        pair_world_box(p, lbox, insts, lo, hi);
+        const double r = insts[p.inst].root_lo[0];
+        return r == r;
     }
 };
 struct LeafRunBox {
     const double* lbox;
-    __device__ __forceinline__ void operator()(int32_t ref, double lo[3], double hi[3]) const {
+    __device__ __forceinline__ bool operator()(int32_t ref, double lo[3], double hi[3]) const {
         const double* b = lbox + 6 * (size_t)~ref;
         for (int k = 0; k < 3; ++k) { lo[k] = b[k]; hi[k] = b[3 + k]; }
+        return true;
     }
 };
+
+// A hidden slot (octant copy 0): near planes +FLT_MAX, far planes -FLT_MAX.  (a) No ray enters it in
+// any octant copy: a copy swaps the rows of an axis with d < 0, so along every axis the near-plane
+// product is +FLT_MAX |1/d| and the far-plane one -FLT_MAX |1/d|; wide_node adds offsets of
+// magnitude at most R (1 + 2^-20) |1/d| with R < 2^27 inside the same FMA (wide.h, set_wide), so
+// with 2^-100 <= |1/d| <= 2^100 every entry term is positive (or +inf), every exit term negative
+// (or -inf), none a NaN, and max(tn, weps) <= min(tf, lim) fails.  (b) pnear[0] < +inf: it is not
+// taken for a structural empty (refit_slot_empty), so k_refit_level visits it again and a later
+// show gives it its box back.  (c) fminf / fmaxf unions are left alone by it, and the union of
+// hidden slots only is the same encoding: an inner slot with nothing visible below is hidden too.
+// k_octant_copies' sort key of such a slot is 0.5 (FLT_MAX - FLT_MAX) = 0 per axis: finite, it sorts
+// among the slots whose centre projects to the origin, before the structural empties.
+constexpr float kHiddenNear = 3.402823466e+38f, kHiddenFar = -3.402823466e+38f;
+__device__ __forceinline__ bool refit_slot_hidden(const W4Node& n, int c) { return n.pnear[0][c] > n.pfar[0][c] && n.pnear[0][c] < HUGE_VALF; }
 
 // One thread per slot of the level's `count` nodes list[0 .. count) (octant copy 0): an inner slot
 // takes the union of its child node's slots, a terminal slot its box rounded outward to float.
@@ -230,8 +250,11 @@ __global__ __launch_bounds__(256) void k_refit_level(W4Node* nodes, const int32_
         refit_slot_union(nodes[ref], lo, hi);
     } else {
         double wlo[3], whi[3];
-        terminal(ref, wlo, whi);
-        for (int k = 0; k < 3; ++k) { lo[k] = refit_down(wlo[k]); hi[k] = refit_up(whi[k]); }
+        const bool visible = terminal(ref, wlo, whi);
+        for (int k = 0; k < 3; ++k) {
+            lo[k] = visible ? refit_down(wlo[k]) : kHiddenNear;
+            hi[k] = visible ? refit_up(whi[k]) : kHiddenFar;
+        }
     }
     for (int k = 0; k < 3; ++k) { n.pnear[k][c] = lo[k]; n.pfar[k][c] = hi[k]; }
 }

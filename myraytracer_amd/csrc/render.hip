@@ -1426,6 +1426,10 @@ struct rt_scene {
         bool has_nrm = false;
     };
     std::vector<StagedDeform> staged_deform;
+    // instance visibility staged by rt_scene_set_instance(s)_visible until rt_scene_commit: empty, or
+    // per instance -1 (nothing staged) / 0 / 1; shown, hidden and forced_rebuild of the last commit
+    std::vector<int8_t> staged_vis;
+    rt_visibility_stats last_vis{};
     rt_deform_stats last_deform{};
     rt_rebuild_stats last_rebuild{};                  // of the last successful commit (rt_scene_commit_ex)
     rt_rebuild_detail last_detail{};                  // ... and which builder made the tree (rt_scene_last_rebuild_detail)
@@ -1783,7 +1787,7 @@ static void set_wide(const HostScene& S, const DeviceReplica& r, RenderParams& P
     P.winst = S.winst.empty() ? nullptr : r.winst;          // transformed scenes (wide.h tw_walk)
     P.tw_tlas_nodes = (int32_t)S.tw_tlas_nodes;
     P.tw_wscale = (float)((double)scale_permille * 1e-3);
-    const bool has_fit = S.fit_root >= 0 && !S.fpairs.empty() && r.fpairs && !S.dyn.fit_blocked;
+    const bool has_fit = S.fit_root >= 0 && !S.fpairs.empty() && r.fpairs && !S.dyn.fit_blocked && !S.dyn.fit_incomplete;
     // the fit tree's magnitudes and its extra widening count only when the fit walk is on: with
     // option fit = 0 the render is the plain tw_walk, and a large fit_coord does not cost it P.wide
     const bool use_fit = has_fit && fit;
@@ -1818,7 +1822,8 @@ static RenderParams make_params(const rt_scene* s, const DeviceReplica& r, int32
     P.mats = r.mats; P.plights = r.plights;
     for (int k = 0; k < 3; ++k) { P.tlas_root_lo[k] = S.tlas_root_lo[k]; P.tlas_root_hi[k] = S.tlas_root_hi[k]; }
     P.tlas_root_ref = S.tlas_root_ref;
-    P.has_tlas = S.has_tlas ? 1 : 0;
+    // every instance hidden: the scene without objects (rtcore.h "instance visibility")
+    P.has_tlas = (S.has_tlas && !(S.dynamic && S.dyn.n_visible == 0)) ? 1 : 0;
     P.tlas_leaf_base = (int32_t)S.tlas_leaf_base;
     P.identity = S.identity ? 1 : 0;
     // one stack for TLAS + BLAS + a TLAS leaf's markers (HostScene::max_stack_unified)

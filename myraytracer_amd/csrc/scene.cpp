@@ -1575,7 +1575,10 @@ int32_t build_host_scene(const rt_scene_desc* d, HostScene& S, std::string& err)
         }
         Y.inst_blas.resize(insts.size());
         for (size_t i = 0; i < insts.size(); ++i) Y.inst_blas[i] = insts[i].blas;
-        if (!S.compact_tris) {                      // no CTri: the triangles' exact local boxes
+        Y.visible.assign(insts.size(), 1);
+        Y.in_tree.assign(insts.size(), 1);
+        Y.n_visible = (int64_t)insts.size();
+        if (!S.compact_tris) {                     // no CTri: the triangles' exact local boxes
             Y.pbox.resize(6 * S.tris.size());
             for (size_t q = 0; q < S.tris.size(); ++q) {
                 const Tri& t = triangles[S.tris[q].prim];
@@ -1701,14 +1704,30 @@ int32_t refit_host_scene(HostScene& S, std::string& err) {
         double* hi = &tb.hi[3 * i];
         if (tb.isLeaf(i) || tb.nodesUsed == 0) {
             for (int k = 0; k < 3; ++k) { lo[k] = kInf; hi[k] = -kInf; }
+            int64_t shown = 0;
             for (int64_t p = 0; p < tb.count[i]; ++p) {
-                const double* b = &S.inst_bounds[6 * (size_t)tb.primIdx[tb.leftFirst[i] + p]];
+                const size_t inst = (size_t)tb.primIdx[tb.leftFirst[i] + p];
+                if (!Y.is_visible(inst)) continue;           // a hidden instance is in no box
+                ++shown;
+                const double* b = &S.inst_bounds[6 * inst];
                 for (int k = 0; k < 3; ++k) { lo[k] = std::fmin(lo[k], b[k]); hi[k] = std::fmax(hi[k], b[3 + k]); }
             }
-            // DWideInst::tbox: the box of the TLAS leaf holding the instance (layout.h)
+            // A leaf without a visible instance takes a box of NaNs: every slab test of it fails
+            // (an inverted box would pass: min / max of its plane distances give the whole line),
+            // and fmin / fmax leave it out of its ancestors' unions, which are NaN only when
+            // nothing below them is visible either.
+            if (shown == 0)
+                for (int k = 0; k < 3; ++k) lo[k] = hi[k] = std::numeric_limits<double>::quiet_NaN();
+            // DWideInst::tbox: the box of the TLAS leaf holding the instance (layout.h); NaNs for a
+            // hidden one (refit.h TreeSlotBox knows a hidden marker by them)
             for (int64_t p = 0; p < tb.count[i] && !S.winst.empty(); ++p) {
-                double* t = S.winst[(size_t)tb.primIdx[tb.leftFirst[i] + p]].tbox;
-                for (int k = 0; k < 3; ++k) { t[k] = lo[k]; t[3 + k] = hi[k]; }
+                const size_t inst = (size_t)tb.primIdx[tb.leftFirst[i] + p];
+                double* t = S.winst[inst].tbox;
+                const bool vis = Y.is_visible(inst);
+                for (int k = 0; k < 3; ++k) {
+                    t[k] = vis ? lo[k] : std::numeric_limits<double>::quiet_NaN();
+                    t[3 + k] = vis ? hi[k] : std::numeric_limits<double>::quiet_NaN();
+                }
             }
         } else {
             const int64_t L = tb.leftFirst[i], R = L + 1;
@@ -1748,6 +1767,7 @@ int32_t refit_host_scene(HostScene& S, std::string& err) {
     double pruneK = 0.0, fitCoord = 0.0;
     bool blocked = false;
     for (size_t i = 0; i < n; ++i) {
+        if (!Y.is_visible(i)) continue;                      // the constants are those of the visible scene
         const double* b = &S.inst_bounds[6 * i];
         for (int k = 0; k < 3; ++k) { wlo[k] = std::fmin(wlo[k], b[k]); whi[k] = std::fmax(whi[k], b[3 + k]); }
         const DInstance& di = S.insts[i];

@@ -66,6 +66,14 @@ struct DynScene {
     std::vector<double> pbox;              // 6 per TriRec: the triangle's exact local box (when the
                                            // scene has no CTri; dropped after upload)
     bool fit_blocked = false;              // an instance exceeds kFitKappa: tw_walk until a commit passes
+    // instance visibility (rtcore.h "instance visibility").  A hidden instance keeps
+    // its real DInstance, inst_bounds and bcoord here; refit_host_scene leaves it out of every union
+    // and constant, and the device copy of its DInstance carries a NaN root box (commit.h).
+    std::vector<uint8_t> visible;          // per instance, as of the last commit (empty: all visible)
+    std::vector<uint8_t> in_tree;          // per instance: the flattened instance tree in use holds its pairs
+    int64_t n_visible = 0;
+    bool fit_incomplete = false;           // a visible instance is not in the tree: tw_walk until a rebuild succeeds
+    bool is_visible(size_t i) const { return visible.empty() || visible[i] != 0; }
 };
 
 // ---- deformable scenes (rt_scene_create_ex with RT_SCENE_DEFORMABLE; deform.h) ---------------------

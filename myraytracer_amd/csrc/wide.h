@@ -263,6 +263,13 @@ struct TwParked {
 // gets one.  On request (rt_scene_commit_ex, RT_COMMIT_REBUILD_FIT) a commit builds this tree again
 // on the device for the pose just committed (rebuild.h): another topology over the same pairs, with
 // the same slot-box conventions, so the argument above holds for it word for word.
+// Hidden instances (rtcore.h "instance visibility") need no code here: the device
+// copy of a hidden instance's DInstance has a BLAS root box of NaNs, every plane distance of which
+// is a NaN, so the root-box slab_hit below (and tw_walk's, and device.h's four) is false in its FAST
+// and its NaN-asymmetric form alike and no primitive of the instance is ever accepted; the hidden
+// slot encoding of refit.h (kHiddenNear) and the NaN tbox only keep rays from getting that far.
+// A rebuilt tree holds the visible pairs only; set_wide withholds it (tw_walk instead) whenever a
+// visible pair is missing from it.
 __device__ __forceinline__ bool fit_boxes_exact(const RenderParams& P, int k, int t0, const V3& o, const V3& d,
                                                 const V3& ol, const V3& dl) {
     const DWideInst& WI = P.winst[k];

@@ -250,6 +250,59 @@ class RayTracerEngine:
         _check(load_library().rt_scene_fit_cost(self._h, C.byref(c)))
         return float(c.value)
 
+    # -- instance visibility (rtcore.h "instance visibility")
+    def set_visible(self, object_index: int, visible: bool):
+        """Stage hiding (False) or showing (True) the instance of scene object `object_index`;
+        commit() applies it.  Instance and object indices never change."""
+        k = self.instance_of(object_index) if self.dynamic else 0
+        if k < 0:
+            raise RenderError(A.RT_ERR_INVALID_ARG, f"object {object_index} produced no instance")
+        _check(load_library().rt_scene_set_instance_visible(self._h, k, 1 if visible else 0))
+
+    def set_visible_many(self, object_indices, visible):
+        """set_visible for several objects: `visible` is one flag for all, or one per object.
+        Objects whose instances are consecutive go down in one rt_scene_set_instances_visible call."""
+        objs = [int(o) for o in object_indices]
+        flags = [bool(visible)] * len(objs) if isinstance(visible, (bool, int, np.bool_)) else [bool(v) for v in visible]
+        if len(flags) != len(objs):
+            raise ValueError("one flag per object")
+        inst = [self.instance_of(o) if self.dynamic else 0 for o in objs]
+        for o, k in zip(objs, inst):
+            if k < 0:
+                raise RenderError(A.RT_ERR_INVALID_ARG, f"object {o} produced no instance")
+        lib, q = load_library(), 0
+        while q < len(inst):
+            e = q + 1
+            while e < len(inst) and inst[e] == inst[e - 1] + 1:
+                e += 1
+            buf = (C.c_uint8 * (e - q))(*[1 if f else 0 for f in flags[q:e]])
+            _check(lib.rt_scene_set_instances_visible(self._h, inst[q], e - q, buf))
+            q = e
+
+    def is_visible(self, object_index: int) -> bool:
+        """Whether the instance of scene object `object_index` is visible, as of the last commit()."""
+        k = self.instance_of(object_index) if self.dynamic else -1
+        if k < 0:
+            raise RenderError(A.RT_ERR_INVALID_ARG, f"object {object_index} produced no instance")
+        v = C.c_int32(0)
+        _check(load_library().rt_scene_instance_visible(self._h, k, C.byref(v)))
+        return bool(v.value)
+
+    def last_visibility_stats(self) -> A.rt_visibility_stats:
+        """Instance and pair counts after the last commit(), what it showed and hid, whether it rebuilt
+        the flattened instance tree on its own and whether that tree holds every visible pair
+        (rt_scene_last_visibility_stats)."""
+        st = A.rt_visibility_stats()
+        _check(load_library().rt_scene_last_visibility_stats(self._h, C.byref(st)))
+        return st
+
+    def visible_scene(self) -> Scene:
+        """A Scene holding only the objects whose instance is visible as of the last commit(), in
+        scene order with their current transforms: the reference scene of the committed state
+        (oracle.OracleScene(eng.visible_scene())); see visible_subset."""
+        return visible_subset(self.scene, [self.instance_of(i) >= 0 and self.is_visible(i)
+                                           for i in range(len(self.scene.objects))])
+
     # -- deforming meshes (BVHBuilder.refit applied to a BLAS, BVH.swift:254-291)
     def vertex_count(self, object_index: int) -> int:
         """The vertex count of mesh object `object_index` (rt_scene_mesh_vertex_count)."""
@@ -603,6 +656,36 @@ class RayTracerEngine:
         the dict of wide_build()."""
         lib = load_library()
         return _wide_dump(lambda io: lib.rt_debug_wide_read(self._h, int(slot), C.byref(io)))
+
+
+def visible_subset(scene: Scene, keep) -> Scene:
+    """A shallow copy of `scene` holding only the objects whose `keep` flag is set, in scene order.
+    A MeshInstance kept while its base mesh is not is written as a Mesh of its own, with the base's
+    triangles, shading and triangle motion blur and the instance's id, matrix and material (a Mesh
+    has no instance motion: a MeshInstance's motion_blur is not carried over)."""
+    import copy
+    from .scene import Mesh, MeshInstance
+    keep = [bool(k) for k in keep]
+    if len(keep) != len(scene.objects):
+        raise ValueError("one flag per object")
+    kept_mesh = {o.id for o, k in zip(scene.objects, keep) if k and isinstance(o, Mesh)}
+    base = {o.id: o for o in scene.objects if isinstance(o, Mesh)}
+    objs = []
+    for o, k in zip(scene.objects, keep):
+        if not k:
+            continue
+        if isinstance(o, MeshInstance) and o.base_mesh_id not in kept_mesh and o.base_mesh_id in base:
+            b = base[o.base_mesh_id]
+            m = copy.copy(b)
+            m.id = o.id
+            m.material = o.material if o.material not in (None, "") else b.material
+            m.transform = o.transform
+            objs.append(m)
+        else:
+            objs.append(o)
+    out = copy.copy(scene)
+    out.objects = objs
+    return out
 
 
 _WIDE_SCALARS = ("wnodes", "wide_copy", "tris", "pairs", "instances", "tw_tlas_nodes", "fit_nodes", "marker_base",
