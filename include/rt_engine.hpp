@@ -169,7 +169,13 @@ public:
         cams_.at((size_t)index) = camera;
     }
     /* commit(true) also builds the flattened instance tree again on the device for the new pose
-     * (RT_COMMIT_REBUILD_FIT); lastRebuildStats() says what the last commit did for it. */
+     * (RT_COMMIT_REBUILD_FIT); lastRebuildStats() says what the last commit did for it.
+     * A commit that throws RT_ERR_INVALID_ARG or RT_ERR_OOM changed nothing (what was staged is
+     * dropped, the last*Stats() keep the last successful commit's); without memory for a rebuild it
+     * returns normally with lastRebuildStats().reason == RT_REBUILD_NO_MEMORY and the old tree refit;
+     * a commit that throws RT_ERR_DEVICE lost the scene: every later render, submit, query, commit,
+     * fitCost and read-back of this engine throws RT_ERR_DEVICE too - destroy it and build a new one
+     * (rtcore.h "how a commit ends"). */
     rt_commit_stats commit(bool rebuild = false) {
         rt_commit_stats st{};
         check(rebuild ? rt_scene_commit_ex(scene_, RT_COMMIT_REBUILD_FIT, &st) : rt_scene_commit(scene_, &st));

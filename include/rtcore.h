@@ -241,7 +241,28 @@ int32_t rt_scene_info_get(const rt_scene* scene, rt_scene_info* out);
  * rt_scene_commit and rt_scene_set_camera return RT_ERR_BUSY, and change nothing, while a render
  * submitted with rt_render_submit has not been waited for.  Renders enqueued with rt_render_device
  * on caller streams are the caller's to order: synchronise those streams before a commit or a
- * camera change.  Both calls drop the measured tile orders (option tile_order) they make stale. */
+ * camera change.  Both calls drop the measured tile orders (option tile_order) they make stale.
+ *
+ * How a commit ends.  rt_scene_commit / rt_scene_commit_ex end in exactly one of four ways:
+ *   1  Done: RT_OK.
+ *   2  Refused, or out of memory, before anything changed: RT_ERR_INVALID_ARG, or RT_ERR_OOM for
+ *      every host or device allocation (every device allocation the commit needs short of a
+ *      rebuild, on every replica, is made before the first kernel that writes scene memory).  Every
+ *      replica and the host are exactly what they were; everything staged is dropped;
+ *      rt_scene_last_deform_stats, rt_scene_last_rebuild_stats, rt_scene_last_rebuild_detail and
+ *      rt_scene_last_visibility_stats keep reporting the last SUCCESSFUL commit.  (RT_ERR_BUSY,
+ *      RT_ERR_UNSUPPORTED and unknown flags return before the staging is touched: it is kept.)
+ *   3  The pose committed, the flattened instance tree not rebuilt for want of memory: RT_OK with
+ *      rt_rebuild_stats.rebuilt = 0 and reason = RT_REBUILD_NO_MEMORY, for every allocation of the
+ *      rebuild, the tree-cost scratch included.  The old tree is refit for the new pose; when the
+ *      rebuild was forced by showing an instance the tree lacks, fit_complete stays 0 and the walks
+ *      stay on the TLAS's marker tree until a later rebuild succeeds.
+ *   4  The scene lost: a HIP runtime error (a failed launch, copy or synchronisation), or any
+ *      failure once the commit has begun to write.  The commit returns RT_ERR_DEVICE, and from then
+ *      on every render, submit, query, commit, rt_scene_fit_cost and debug read-back of that scene
+ *      returns RT_ERR_DEVICE with a message that names the failed commit; the scene never returns a
+ *      frame again.  No rollback is attempted (the host keeps no old vertex positions).
+ *      rt_scene_destroy and the rt_scene_last_* getters still work; other scenes are unaffected. */
 #define RT_SCENE_DYNAMIC 1u
 int32_t rt_scene_create_ex(const rt_scene_desc* desc, const int32_t* devices, int32_t n_devices,
                            uint32_t flags, rt_scene** out);
@@ -286,9 +307,10 @@ int32_t rt_scene_commit(rt_scene* scene, rt_commit_stats* stats /* may be NULL *
  *       NaN in a vertex no triangle references is refused too: every value must be finite, and for
  *       every instance of the mesh reach * (3 * c + 1) < 1e30 must hold (reach: the largest |entry| of
  *       its staged or current matrix; c: the largest |coordinate| plus the largest |motionBlur|
- *       component).  On failure: RT_ERR_INVALID_ARG, everything staged is dropped, nothing changed.
- *   rt_scene_last_deform_stats   what the last rt_scene_commit did for deformations (zeros when it
- *                                had none staged).  rt_commit_stats keeps its meaning; its total_ms
+ *       component).  On failure: RT_ERR_INVALID_ARG, everything staged is dropped, nothing changed
+ *       ("how a commit ends" above).
+ *   rt_scene_last_deform_stats   what the last successful rt_scene_commit did for deformations
+ *                                (zeros when it had none staged).  rt_commit_stats keeps its meaning; its total_ms
  *                                includes this work.
  * After a deformation rt_debug_bvh_hash still reports the build's hash. */
 #define RT_SCENE_DEFORMABLE 2u      /* rt_scene_create_ex flag; implies RT_SCENE_DYNAMIC */
@@ -303,7 +325,7 @@ typedef struct rt_deform_stats {
     double deform_ms;           /* triangles, triangle boxes, normals, leaf boxes       */
     double blas_refit_ms;       /* BLAS records, four-wide BLAS nodes, root box read-back */
 } rt_deform_stats;
-int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);   /* of the last commit */
+int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);   /* of the last successful commit */
 
 /* ---- rebuilding the flattened instance tree (appended under ABI 5; detect by symbol) -----------
  * A commit keeps the topology of every tree, chosen for the pose the scene was created at.  For the
@@ -342,8 +364,9 @@ int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);
  *       tree (spheres or planes, motion blur, fewer than two pairs), when the tree is blocked by an
  *       instance whose transform exceeds the conditioning bound, when the new tree would be deeper
  *       than the traversal stack allows (or than the test hook rebuild_depth_cap), when its node
- *       array would reach 4 GB, or when a device allocation fails.  The old tree then stays in place,
- *       refit as by a plain commit.
+ *       array would reach 4 GB, or when an allocation of the rebuild fails (RT_REBUILD_NO_MEMORY: the
+ *       tree-cost scratch, the live-pair buffer, the arena, the new nodes and levels, on any replica).
+ *       The old tree then stays in place, refit as by a plain commit.
  *   rt_scene_last_rebuild_stats   what the last successful commit did for a rebuild (zeros when it
  *       asked for none).  rt_commit_stats.total_ms includes the rebuild; build_ms includes the clustering.
  *   rt_scene_last_rebuild_detail  which builder made the tree of that commit (zeros when it asked for
@@ -353,7 +376,8 @@ int32_t rt_scene_last_deform_stats(const rt_scene* scene, rt_deform_stats* out);
  *       slots of its nodes, of the slot box's surface area, over the area of the union of the root's
  *       slots (lower is better; what a ray pays grows with it).  Summed in a fixed order: the value
  *       depends on the tree only.  RT_OK with cost 0 when the scene has no such tree;
- *       RT_ERR_UNSUPPORTED without RT_SCENE_DYNAMIC, RT_ERR_BUSY as rt_scene_commit.
+ *       RT_ERR_UNSUPPORTED without RT_SCENE_DYNAMIC, RT_ERR_BUSY as rt_scene_commit, RT_ERR_OOM when
+ *       its scratch cannot be allocated.
  * Not rebuilt: the reference-form TLAS, the BLASes, the TLAS's four-wide marker tree (option fit = 0).
  * A rebuild holds the pairs of the visible instances only ("instance visibility" below); instances
  * that did not exist at rt_scene_create_ex can still not be added. */
@@ -426,7 +450,7 @@ typedef struct rt_visibility_stats {
     int32_t forced_rebuild;                  /* 1: the commit rebuilt the tree on its own           */
     int32_t fit_complete;                    /* 1: the tree in use holds every visible pair         */
 } rt_visibility_stats;
-int32_t rt_scene_last_visibility_stats(const rt_scene* scene, rt_visibility_stats* out);   /* of the last commit */
+int32_t rt_scene_last_visibility_stats(const rt_scene* scene, rt_visibility_stats* out);   /* of the last successful commit */
 
 /* Render options: tuning and test switches, each default being the production setting.
  *   wide (1)             conservative FP32 four-wide walk of identity scenes (exact: wide.h)
@@ -464,6 +488,16 @@ int32_t rt_scene_get_option(const rt_scene* scene, const char* name, int64_t* va
  *   rebuild_cluster_iter_cap (152)  iterations the clustered builder may take: the smaller of this
  *                             and 4 ceil(log2 pairs) + 32 holds (152 is that cap at 2^30 pairs; it can
  *                             only be lowered): lets a small scene exercise the fall-back to Morton
+ *   debug_fail_commit_alloc (0)  n > 0: the n-th device allocation the next commit attempts reports
+ *                             failure and nothing is allocated for it; counted from 1 over every
+ *                             replica and every allocation the commit has to make (scratch it already
+ *                             holds is not allocated again)
+ *   debug_fail_commit_step (0)   k > 0: the next commit returns as for a HIP runtime error before its
+ *                             step k runs (1 position check, 2 moved bounds, 3 range check, 4 triangles,
+ *                             5 BLAS refit, 6 bounds of the deformed, 7 visibility, 8 host refit,
+ *                             9 upload and tree refit, 10 the rebuild): the scene is lost
+ *                             Both are host-side early returns that launch nothing, are read by the
+ *                             commit alone and clear themselves when it returns.
  * Used only by the parity tests that show the exactness proof has teeth. */
 int32_t rt_scene_set_unsafe_option(rt_scene* scene, const char* name, int64_t value);
 

@@ -221,6 +221,21 @@ int32_t rt_scene_last_rebuild_detail(const rt_scene* s, rt_rebuild_detail* out) 
 
 // ---- shared by the steps ------------------------------------------------------------------------------
 // World bounds of the moved triangle-mesh instances, on replica 0 (refit.h k_inst_bounds)
+// Partial unions k_inst_bounds writes per instance when the largest mesh among them has `most` triangles
+static int bounds_parts(int64_t most) {
+    return (int)std::min<int64_t>(64, (std::max<int64_t>(most, 1) + dev::kBoundsBlock * 8 - 1) / (dev::kBoundsBlock * 8));
+}
+// Replica 0's scratch for the bounds of n instances.  A commit reserves it for both of its
+// reductions before it writes anything (commit_reserve); device_instance_bounds then finds it there.
+static int32_t reserve_instance_bounds(rt_scene* s, int64_t n, int64_t part_doubles) {
+    if (n == 0) return RT_OK;
+    DeviceReplica& r = s->devs[0];
+    HIP_TRY(hipSetDevice(r.device));
+    AllocGate& g = s->gate;
+    if (!r.moves.grow(g, n) || !r.bounds_out.grow(g, 6 * n) || !r.bounds_part.grow(g, part_doubles))
+        return fail(RT_ERR_OOM, "device allocation failed (instance bounds scratch)");
+    return RT_OK;
+}
 static int32_t device_instance_bounds(rt_scene* s, const std::vector<dev::RefitMove>& moves, std::vector<double>& out) {
     DeviceReplica& r = s->devs[0];
     const int64_t n = (int64_t)moves.size();
@@ -229,9 +244,8 @@ static int32_t device_instance_bounds(rt_scene* s, const std::vector<dev::RefitM
     HIP_TRY(hipSetDevice(r.device));
     int64_t most = 1;
     for (const dev::RefitMove& m : moves) most = std::max<int64_t>(most, m.tri_end - m.tri_first);
-    const int parts = (int)std::min<int64_t>(64, (most + dev::kBoundsBlock * 8 - 1) / (dev::kBoundsBlock * 8));
-    if (!r.moves.grow(n) || !r.bounds_out.grow(6 * n) || !r.bounds_part.grow(6 * n * parts))
-        return fail(RT_ERR_DEVICE, "hipMalloc (instance bounds scratch): out of memory");
+    const int parts = bounds_parts(most);
+    COMMIT_TRY(reserve_instance_bounds(s, n, 6 * n * parts));
     HIP_TRY(hipMemcpy(r.moves, moves.data(), (size_t)n * sizeof(dev::RefitMove), hipMemcpyHostToDevice));
     const CTri* ct = s->host.compact_tris ? r.ctris : nullptr;
     if (!ct && !r.pbox) return fail(RT_ERR_DEVICE, "dynamic scene without triangle boxes");
@@ -399,16 +413,15 @@ struct LivePairs {
     int32_t* live = nullptr;
     ~LivePairs() { (void)hipFree(base); }
 };
-static int32_t rebuild_live_pairs(const HostScene& S, DeviceReplica& r, int64_t n_live, LivePairs& lp, RebuiltTree& R) {
+static int32_t rebuild_live_pairs(const HostScene& S, DeviceReplica& r, AllocGate& gate, int64_t n_live, LivePairs& lp,
+                                  RebuiltTree& R) {
     const int64_t n_all = (int64_t)S.fpairs.size();
     hipStream_t st = r.stream;
     auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
     size_t scan_bytes = 0;
     HIP_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, (int32_t*)nullptr, (int32_t*)nullptr, (int)(n_all + 1), st));
     const size_t words = pad((size_t)(n_all + 1) * sizeof(int32_t));
-    if (hipMalloc((void**)&lp.base, 3 * words + pad(scan_bytes)) != hipSuccess) {
-        (void)hipGetLastError();
-        lp.base = nullptr;
+    if (!gate.alloc((void**)&lp.base, 3 * words + pad(scan_bytes))) {
         R.reason = RT_REBUILD_NO_MEMORY;
         return RT_OK;
     }
@@ -432,15 +445,15 @@ static int32_t rebuild_live_pairs(const HostScene& S, DeviceReplica& r, int64_t 
 
 // n_live: the pairs of the visible instances (the host's count); fewer than all of them: the tree is
 // built over those alone
-static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t depth_cap, bool clustered, int64_t iter_cap,
-                              int64_t n_live, RebuiltTree& R) {
+static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, AllocGate& gate, int64_t depth_cap, bool clustered,
+                              int64_t iter_cap, int64_t n_live, RebuiltTree& R) {
     HIP_TRY(hipSetDevice(r.device));
     const auto t0 = CommitClock::now();
     const int64_t n = n_live;
     hipStream_t st = r.stream;
     LivePairs lp;
     if (n_live < (int64_t)S.fpairs.size()) {
-        const int32_t rc = rebuild_live_pairs(S, r, n_live, lp, R);
+        const int32_t rc = rebuild_live_pairs(S, r, gate, n_live, lp, R);
         if (rc != RT_OK || R.reason != RT_REBUILD_NONE) return rc;
     }
     R.live = lp.live;
@@ -454,9 +467,7 @@ static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t dept
         m.scan_bytes = std::max(m.scan_bytes, words);
     }
     const size_t total = m.carve(nullptr, n, parts, clustered ? n : 0);
-    if (hipMalloc((void**)&m.base, total) != hipSuccess) {
-        (void)hipGetLastError();
-        m.base = nullptr;
+    if (!gate.alloc((void**)&m.base, total)) {
         R.reason = RT_REBUILD_NO_MEMORY;
         return RT_OK;
     }
@@ -494,9 +505,8 @@ static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t dept
     // 4. the new node array: the eight main parts as they are, the new fit nodes behind copy 0's,
     //    then their octant copies (over the level list, deepest level first)
     const int64_t n_main = S.fit_root, new_copy = n_main + R.nodes;
-    if (hipMalloc((void**)&R.wnodes, (size_t)(8 * new_copy) * sizeof(W4Node)) != hipSuccess ||
-        hipMalloc((void**)&R.levels, (size_t)R.nodes * sizeof(int32_t)) != hipSuccess) {
-        (void)hipGetLastError();
+    if (!gate.alloc((void**)&R.wnodes, (size_t)(8 * new_copy) * sizeof(W4Node)) ||
+        !gate.alloc((void**)&R.levels, (size_t)R.nodes * sizeof(int32_t))) {
         R.drop();
         R.reason = RT_REBUILD_NO_MEMORY;
         return RT_OK;
@@ -516,11 +526,11 @@ static int32_t rebuild_fit_on(const HostScene& S, DeviceReplica& r, int64_t dept
 
 // The cost of the fit tree replica r holds (rebuild.h k_fit_cost; rt_scene_fit_cost); 0 without one.
 // The partial sums go through the replica's bounds scratch: the scene lock is held.
-static int32_t fit_cost_on(const HostScene& S, DeviceReplica& r, double* cost) {
+static int32_t fit_cost_on(const HostScene& S, DeviceReplica& r, AllocGate& gate, double* cost) {
     *cost = 0.0;
     if (S.fit_root < 0 || S.fit_nodes <= 0 || S.wide_copy <= 0 || !r.wnodes) return RT_OK;
     HIP_TRY(hipSetDevice(r.device));
-    if (!r.bounds_part.grow(dev::kFcBlocks + 1)) return fail(RT_ERR_DEVICE, "hipMalloc (tree cost scratch): out of memory");
+    if (!r.bounds_part.grow(gate, dev::kFcBlocks + 1)) return fail(RT_ERR_OOM, "device allocation failed (tree cost scratch)");
     const W4Node* fit = r.wnodes + S.fit_root;
     hipLaunchKernelGGL(dev::k_fit_cost, dim3(dev::kFcBlocks), dim3(dev::kRbBlock), 0, r.stream, fit, S.fit_nodes, r.bounds_part.p);
     hipLaunchKernelGGL(dev::k_fit_cost_fold, dim3(1), dim3(64), 0, r.stream, (const double*)r.bounds_part.p, dev::kFcBlocks, fit,
@@ -537,9 +547,10 @@ int32_t rt_scene_fit_cost(rt_scene* s, double* cost) {
     *cost = 0.0;
     if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
     std::lock_guard<std::mutex> lock(s->mu);
+    COMMIT_TRY(scene_lost(s));
     if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
     if (s->devs.empty() || s->host.winst.empty()) return RT_OK;
-    return fit_cost_on(s->host, s->devs[0], cost);
+    return fit_cost_on(s->host, s->devs[0], s->gate, cost);
 }
 
 // The rebuild step of a commit (the scene lock is held, no render is in flight).  Returns RT_OK
@@ -568,28 +579,41 @@ static int32_t rebuild_fit(rt_scene* s, bool clustered) {
     for (const DeviceReplica& r : s->devs) tree = tree && r.wnodes && r.fpairs && r.lbox && r.insts;
     if (!tree) return done(RT_REBUILD_NO_TREE);
     if (S.dyn.fit_blocked) return done(RT_REBUILD_BLOCKED);
-    COMMIT_TRY(fit_cost_on(S, s->devs[0], &dt.cost_before));
+    {   // the cost scratch is an allocation of the rebuild like the others: without it the old tree stays
+        const int32_t rc = fit_cost_on(S, s->devs[0], s->gate, &dt.cost_before);
+        if (rc == RT_ERR_OOM) return done(RT_REBUILD_NO_MEMORY);
+        if (rc != RT_OK) return rc;
+    }
     // the clustering gives up after 4 ceil(log2 n) + 32 iterations (the test hook can only lower that)
     int64_t log2n = 0;
     while ((int64_t(1) << log2n) < n_live) ++log2n;
     const int64_t iter_cap = std::min<int64_t>(4 * log2n + 32, s->opt[kOptRebuildClusterIterCap]);
+    std::vector<RebuiltTree> res;
+    auto drop_all = [&]() {
+        for (size_t j = 0; j < res.size(); ++j) {
+            (void)hipSetDevice(s->devs[j].device);
+            res[j].drop();
+        }
+    };
     try {
-        std::vector<RebuiltTree> res(s->devs.size());
+        res.resize(s->devs.size());
         for (size_t k = 0; k < res.size(); ++k) {
-            const int32_t rc = rebuild_fit_on(S, s->devs[k], s->opt[kOptRebuildDepthCap], clustered, iter_cap, n_live, res[k]);
+            const int32_t rc = rebuild_fit_on(S, s->devs[k], s->gate, s->opt[kOptRebuildDepthCap], clustered, iter_cap, n_live, res[k]);
             dt.iterations = std::max(dt.iterations, res[k].iterations);
             dt.fell_back = std::max(dt.fell_back, res[k].fell_back);
             dt.cluster_ms = std::max(dt.cluster_ms, res[k].cluster_ms);
             if (rc == RT_OK && res[k].reason == RT_REBUILD_NONE && res[k].level_count == res[0].level_count) continue;
             const int32_t reason = res[k].reason;
-            for (size_t j = 0; j < res.size(); ++j) {
-                (void)hipSetDevice(s->devs[j].device);
-                res[j].drop();
-            }
+            drop_all();
             if (rc != RT_OK) return rc;
             if (reason != RT_REBUILD_NONE) return done(reason);
             return fail(RT_ERR_DEVICE, "rebuild: the replicas built different trees");
         }
+        // what the host keeps is made before anything is swapped: a host allocation that fails here
+        // still leaves the old tree in use everywhere
+        const RebuiltTree& R0 = res[0];
+        RefitLevels new_levels = levels_from_counts(S.fit_root, R0.level_count);
+        std::vector<uint8_t> new_in_tree = S.dyn.visible;
         for (size_t k = 0; k < res.size(); ++k) {
             DeviceReplica& r = s->devs[k];
             HIP_TRY(hipSetDevice(r.device));
@@ -601,23 +625,25 @@ static int32_t rebuild_fit(rt_scene* s, bool clustered) {
                        (res[k].nodes - (int64_t)std::max<size_t>(1, S.dyn.fit_levels.nodes.size())) * (int64_t)sizeof(int32_t);
             st.sort_ms = std::max(st.sort_ms, res[k].sort_ms);
             st.build_ms = std::max(st.build_ms, res[k].build_ms);
+            res[k].wnodes = nullptr;                        // the replica's now
+            res[k].levels = nullptr;
         }
         // what the host keeps: the counts renders and queries are made from, and the level lists
         // a later plain commit refits
-        const RebuiltTree& R0 = res[0];
-        S.dyn.fit_levels = levels_from_counts(S.fit_root, R0.level_count);
+        S.dyn.fit_levels = std::move(new_levels);
         S.wide_copy = S.fit_root + R0.nodes;
         S.fit_nodes = R0.nodes;
         S.fit_depth = (int64_t)R0.level_count.size();
-        S.dyn.in_tree = S.dyn.visible;                      // the pairs the new tree holds
+        S.dyn.in_tree = std::move(new_in_tree);             // the pairs the new tree holds
         S.dyn.fit_incomplete = false;
         st.nodes_after = S.fit_nodes;
         st.depth_after = S.fit_depth;
         dt.builder = clustered && !dt.fell_back ? 2 : 1;
-        COMMIT_TRY(fit_cost_on(S, s->devs[0], &dt.cost_after));
+        COMMIT_TRY(fit_cost_on(S, s->devs[0], s->gate, &dt.cost_after));
         return done(RT_REBUILD_NONE);
-    } catch (const std::bad_alloc&) {
-        return fail(RT_ERR_OOM, "host allocation failed");
+    } catch (const std::bad_alloc&) {                       // thrown before the swap only
+        drop_all();
+        return done(RT_REBUILD_NO_MEMORY);
     }
 }
 
@@ -635,7 +661,7 @@ struct CommitPlan {
     std::vector<char> later;                      // per staged transform: its instance's mesh deforms, bounds come last
     std::vector<double> nb;                       // per staged transform: the instance's new world bounds
     std::vector<double> roots;                    // per staged deformation: root box[6], max |e1||e2|, 0 (k_blas_root)
-    std::vector<int32_t> rebound;                 // the instances of the deformed meshes ...
+    std::vector<int32_t> rebound;                 // the instances of the deformed meshes, by staged deformation ...
     std::vector<double> rebound_box;              // ... and their new world bounds
     rt_deform_stats dst{};
     rt_visibility_stats vst{};
@@ -666,6 +692,12 @@ struct CommitPlan {
             dst.triangles += nt;
         }
         part_total = std::max(part_total, blocks);
+        // host memory the steps past the first write need is taken here, while a failure changes nothing
+        for (const rt_scene::StagedDeform& sd : sdef)
+            for (size_t i = 0; i < S.dyn.inst_blas.size(); ++i)
+                if (S.dyn.inst_blas[i] == sd.blas) rebound.push_back((int32_t)i);
+        roots.assign(8 * sdef.size(), 0.0);
+        rebound_box.reserve(6 * rebound.size());
     }
     // the matrix instance k has once this commit is through
     const double* matrix_of(const HostScene& S, int32_t k) const {
@@ -702,12 +734,42 @@ static double matrix_reach(const double* m16) {
     return reach;
 }
 
-// The deformation scratch of one replica, and the staged host arrays in its one staging buffer
+// Every device allocation steps 1 - 9 need, made before the first kernel that writes scene memory:
+// a failure here is RT_ERR_OOM with nothing changed on any replica or on the host.  Every replica's
+// deformation scratch, and replica 0's instance-bounds scratch for the larger of its two
+// reductions (the moved instances, commit_moved_bounds; those of the deformed meshes,
+// commit_rebound_deformed).  The arrays are kept, so a commit like the last one allocates nothing.
+static int32_t commit_reserve(rt_scene* s, CommitPlan& P) {
+    const HostScene& S = s->host;
+    AllocGate& g = s->gate;
+    if (!P.sdef.empty())
+        for (DeviceReplica& r : s->devs) {
+            HIP_TRY(hipSetDevice(r.device));
+            if (!r.def_stage.grow(g, P.stage_total) || !r.def_part.grow(g, P.part_total) ||
+                !r.def_out.grow(g, 8 * (int64_t)P.sdef.size()) || !r.def_face.grow(g, P.face_need) ||
+                !r.def_vnorm.grow(g, P.vnorm_need))
+                return fail(RT_ERR_OOM, "device allocation failed (deformation scratch)");
+        }
+    auto tris_of = [&](int32_t k) {
+        const DynBlas& y = S.dyn.blas[(size_t)S.dyn.inst_blas[(size_t)k]];
+        return y.tri_end - y.tri_first;
+    };
+    int64_t moved = 0, moved_most = 1, rebound_most = 1;
+    for (const auto& e : P.staged) {
+        const int32_t blas = S.dyn.inst_blas[(size_t)e.first];
+        if (S.dyn.blas[(size_t)blas].kind != kPrimTriangles || P.deformed[(size_t)blas]) continue;
+        ++moved;
+        moved_most = std::max<int64_t>(moved_most, tris_of(e.first));
+    }
+    const int64_t rebound = (int64_t)P.rebound.size();
+    for (const int32_t k : P.rebound) rebound_most = std::max<int64_t>(rebound_most, tris_of(k));
+    return reserve_instance_bounds(s, std::max(moved, rebound),
+                                   std::max(6 * moved * bounds_parts(moved_most), 6 * rebound * bounds_parts(rebound_most)));
+}
+
+// The staged host arrays in a replica's staging buffer (commit_reserve made it)
 static int32_t stage_replica(DeviceReplica& r, const CommitPlan& P) {
     HIP_TRY(hipSetDevice(r.device));
-    if (!r.def_stage.grow(P.stage_total) || !r.def_part.grow(P.part_total) || !r.def_out.grow(8 * (int64_t)P.sdef.size()) ||
-        !r.def_face.grow(P.face_need) || !r.def_vnorm.grow(P.vnorm_need))
-        return fail(RT_ERR_OOM, "device allocation failed (deformation scratch)");
     for (size_t m = 0; m < P.sdef.size(); ++m) {
         const rt_scene::StagedDeform& sd = P.sdef[m];
         if (!sd.pos.empty())
@@ -797,10 +859,12 @@ static int32_t commit_deform_triangles(rt_scene* s, CommitPlan& P) {
     const HostScene& S = s->host;
     const auto t = CommitClock::now();
     const dim3 block(dev::kDeformBlock);
-    for (DeviceReplica& r : s->devs) {
-        if (&r != &s->devs[0]) COMMIT_TRY(stage_replica(r, P));
-        HIP_TRY(hipSetDevice(r.device));
+    for (DeviceReplica& r : s->devs) {                      // before the first launch: what can still fail cleanly
         if (!r.pbox || !r.vid) return fail(RT_ERR_DEVICE, "deformable scene without triangle boxes");
+        if (&r != &s->devs[0]) COMMIT_TRY(stage_replica(r, P));
+    }
+    for (DeviceReplica& r : s->devs) {
+        HIP_TRY(hipSetDevice(r.device));
         for (size_t m = 0; m < P.sdef.size(); ++m) {
             const DeformBlas& f = S.def.blas[(size_t)P.sdef[m].blas];
             const DynBlas& y = S.dyn.blas[(size_t)P.sdef[m].blas];
@@ -860,7 +924,6 @@ static int32_t commit_refit_blas(rt_scene* s, CommitPlan& P) {
         HIP_TRY(hipGetLastError());
     }
     COMMIT_TRY(sync_replicas(s));
-    P.roots.assign(8 * nd, 0.0);
     HIP_TRY(hipSetDevice(s->devs[0].device));
     HIP_TRY(hipMemcpy(P.roots.data(), s->devs[0].def_out, P.roots.size() * sizeof(double), hipMemcpyDeviceToHost));
     P.dst.blas_refit_ms = ms_since(t);
@@ -874,7 +937,10 @@ static int32_t commit_rebound_deformed(rt_scene* s, CommitPlan& P) {
     if (P.sdef.empty()) return RT_OK;
     HostScene& S = s->host;
     const auto t = CommitClock::now();
+    // the device first: the host's copies are written once nothing can fail any more
     std::vector<dev::RefitMove> moves;
+    for (const int32_t i : P.rebound) moves.push_back(move_for(S, i, P.matrix_of(S, i)));
+    COMMIT_TRY(device_instance_bounds(s, moves, P.rebound_box));
     for (size_t m = 0; m < P.sdef.size(); ++m) {
         const double* o = &P.roots[8 * m];
         S.dyn.blas[(size_t)P.sdef[m].blas].P = o[6];
@@ -885,11 +951,8 @@ static int32_t commit_rebound_deformed(rt_scene* s, CommitPlan& P) {
             DInstance& di = S.insts[i];
             for (int a = 0; a < 3; ++a) { di.root_lo[a] = o[a]; di.root_hi[a] = o[3 + a]; }
             if (!S.winst.empty()) S.winst[i].bcoord = bc;
-            moves.push_back(move_for(S, (int32_t)i, P.matrix_of(S, (int32_t)i)));
-            P.rebound.push_back((int32_t)i);
         }
     }
-    COMMIT_TRY(device_instance_bounds(s, moves, P.rebound_box));
     P.bounds_ms += ms_since(t);
     P.dst.meshes_deformed = (int64_t)P.sdef.size();
     P.dst.instances_rebounded = (int64_t)P.rebound.size();
@@ -960,6 +1023,16 @@ static int32_t commit_upload_and_refit(rt_scene* s, CommitPlan&) {
 }
 
 // ---- the driver ------------------------------------------------------------------------------------
+// A commit ends in one of four ways (rtcore.h "how a commit ends"):
+//   1  done.
+//   2  refused (RT_ERR_INVALID_ARG) or out of memory (RT_ERR_OOM) before anything changed: every
+//      replica, the host and the last_* stats are what they were; what was staged is dropped.
+//   3  the pose committed, the tree not rebuilt for want of memory: RT_OK, RT_REBUILD_NO_MEMORY.
+//   4  the scene lost: any failure once the first writing step has begun, and any HIP runtime
+//      error (also before that: the device is in no known state).  RT_ERR_DEVICE now and from
+//      every later call on the scene (scene_lost); no rollback, the host keeps no old positions.
+// The steps are numbered for the test hook debug_fail_commit_step: 1 - 9 below, 10 the rebuild.
+static int32_t commit_steps(rt_scene* s, bool rebuild, bool clustered, rt_commit_stats* stats, bool& wrote);
 static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) {
     if (stats) *stats = rt_commit_stats{};
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
@@ -968,31 +1041,59 @@ static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) 
     const bool rebuild = clustered || (flags & RT_COMMIT_REBUILD_FIT) != 0;
     if (!s->host.dynamic) return fail(RT_ERR_UNSUPPORTED, "not a dynamic scene (rt_scene_create_ex, RT_SCENE_DYNAMIC)");
     std::lock_guard<std::mutex> lock(s->mu);
+    COMMIT_TRY(scene_lost(s));
     if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
+    // the test hooks hold for this commit alone
+    s->gate.fail_at = s->opt[kOptDebugFailCommitAlloc];
+    s->gate.count = 0;
+    bool wrote = false;
+    int32_t rc = commit_steps(s, rebuild, clustered, stats, wrote);
+    s->gate.fail_at = 0;
+    s->opt[kOptDebugFailCommitAlloc] = s->opt[kOptDebugFailCommitStep] = 0;
+    if (rc != RT_OK && (wrote || rc == RT_ERR_DEVICE)) {
+        s->lost.store(true);
+        rc = fail(RT_ERR_DEVICE, "rt_scene_commit failed on the device and the scene is lost (" + g_err +
+                                     "): every later call on it fails; rt_scene_destroy it and create it again");
+    }
+    return rc;
+}
+static int32_t commit_steps(rt_scene* s, bool rebuild, bool clustered, rt_commit_stats* stats, bool& wrote) {
     const auto t0 = CommitClock::now();
-    s->last_deform = rt_deform_stats{};
+    const int64_t fail_step = s->opt[kOptDebugFailCommitStep];
+    auto injected = [&](int k) {
+        return fail_step != k ? (int32_t)RT_OK
+                              : fail(RT_ERR_DEVICE, "injected failure before step " + std::to_string(k) +
+                                                        " (option debug_fail_commit_step)");
+    };
     if (s->staged.empty() && s->staged_deform.empty() && s->staged_vis.empty()) {
-        s->last_vis = rt_visibility_stats{};
-        int32_t rc = RT_OK;
         if (rebuild) {                                       // nothing staged: the pose as it stands
-            rc = rebuild_fit(s, clustered);
-            if (rc == RT_OK) drop_tile_orders(s);
+            COMMIT_TRY(injected(10));
+            COMMIT_TRY(rebuild_fit(s, clustered));
+            drop_tile_orders(s);
         } else {
             s->last_rebuild = rt_rebuild_stats{};
             s->last_detail = rt_rebuild_detail{};
         }
+        s->last_deform = rt_deform_stats{};
+        s->last_vis = rt_visibility_stats{};
         if (stats) stats->total_ms = ms_since(t0);
-        return rc;
+        return RT_OK;
     }
     try {
         CommitPlan P(s, t0);
-        // checked before anything changes, then the deformations on the device
+        COMMIT_TRY(commit_reserve(s, P));
+        // 1 - 3 check before anything changes; from 4 on the scene is written: the deformations on the
+        // device (4 - 6), then the transforms and visibility on the host and on every replica (7 - 9)
+        int k = 0;
+        CommitClock::time_point t1;
         for (auto step : {commit_validate_positions, commit_moved_bounds, commit_range_check, commit_deform_triangles,
-                          commit_refit_blas, commit_rebound_deformed})
+                          commit_refit_blas, commit_rebound_deformed, commit_apply_visibility, commit_host_refit,
+                          commit_upload_and_refit}) {
+            COMMIT_TRY(injected(++k));
+            if (k == 4) wrote = true;
+            if (k == 7) t1 = CommitClock::now();
             COMMIT_TRY(step(s, P));
-        // the transforms: the host's structures, then every replica's
-        const auto t1 = CommitClock::now();
-        for (auto step : {commit_apply_visibility, commit_host_refit, commit_upload_and_refit}) COMMIT_TRY(step(s, P));
+        }
         drop_tile_orders(s);
         s->last_deform = P.dst;
         s->last_vis = P.vst;
@@ -1005,6 +1106,7 @@ static int32_t commit_impl(rt_scene* s, uint32_t flags, rt_commit_stats* stats) 
         Y.fit_incomplete = !complete;
         // on request the flattened instance tree again, from the pose just committed
         if (rebuild || !complete) {
+            COMMIT_TRY(injected(10));
             COMMIT_TRY(rebuild_fit(s, clustered));
             s->last_vis.forced_rebuild = (!rebuild && s->last_rebuild.rebuilt) ? 1 : 0;
         } else {

@@ -1253,15 +1253,28 @@ struct TileOrder {
 
 // Commit scratch (commit.h): touched by no render (commits never run beside renders), so it is replaced
 // outright when it has to grow - no 1.5x growth, no retire list - and scratch_bytes does not count it.
+// Every device allocation a commit makes goes through the scene's AllocGate, so that the test hook
+// debug_fail_commit_alloc can make the fail_at-th of them report failure (nothing is allocated for it).
+struct AllocGate {
+    int64_t fail_at = 0, count = 0;           // fail_at 0: none fails; count: attempts since commit_impl armed it
+    bool alloc(void** p, size_t bytes) {
+        *p = nullptr;
+        if (++count == fail_at) return false;
+        if (hipMalloc(p, bytes) == hipSuccess) return true;
+        (void)hipGetLastError();
+        *p = nullptr;
+        return false;
+    }
+};
 template <class T>
 struct DevArray {
     T* p = nullptr;
     int64_t cap = 0;                          // elements
-    bool grow(int64_t need) {
+    bool grow(AllocGate& gate, int64_t need) {
         if (need <= cap && p) return true;
         release();
         need = std::max<int64_t>(need, 1);
-        if (hipMalloc((void**)&p, (size_t)need * sizeof(T)) != hipSuccess) { (void)hipGetLastError(); p = nullptr; return false; }
+        if (!gate.alloc((void**)&p, (size_t)need * sizeof(T))) return false;
         cap = need;
         return true;
     }
@@ -1355,7 +1368,7 @@ enum OptId {
     kOptQueue, kOptQueueLevels, kOptHitlog, kOptNodeshade, kOptLevels, kOptTreePpw, kOptFullFlights,
     kOptDeepCapMb, kOptBatches, kOptZerocopy, kOptSubmitEvents, kOptSubmitCounters, kOptSubmitDma,
     kOptDebugFailReplica, kOptWideDeltaScale, kOptNodeLists, kOptTileOrder, kOptFit, kOptQueueTail, kOptQueryBatch,
-    kOptRebuildDepthCap, kOptRebuildClusterIterCap,
+    kOptRebuildDepthCap, kOptRebuildClusterIterCap, kOptDebugFailCommitAlloc, kOptDebugFailCommitStep,
     kOptCount
 };
 // `unsafe` options are test hooks: rt_scene_set_option refuses them (RT_ERR_INVALID_ARG); only the
@@ -1396,6 +1409,11 @@ static const OptDef kOptDefs[kOptCount] = {
     {"rebuild_cluster_iter_cap", 4 * 30 + 32, 1, 4 * 30 + 32, true},            // test hook: iterations the clustered builder may take
                                                                                 // (rebuild_fit takes the smaller of it and 4 ceil(log2 pairs) + 32;
                                                                                 // the default is that cap at 2^30 pairs, the most a tree holds)
+    {"debug_fail_commit_alloc", 0, 0, 1 << 20, true},   // test hook: the n-th device allocation of the next commit reports failure
+                                                        // (counted from 1 over every replica; commit.h AllocGate users); 0 = off
+    {"debug_fail_commit_step", 0, 0, 10, true},         // test hook: the next commit returns as for a HIP error before its step k
+                                                        // (commit_impl's steps 1 .. 9 in order, 10 the rebuild); 0 = off.  Both are
+                                                        // read by commit_impl only and cleared when that commit returns
 };
 
 struct rt_scene {
@@ -1433,7 +1451,18 @@ struct rt_scene {
     rt_deform_stats last_deform{};
     rt_rebuild_stats last_rebuild{};                  // of the last successful commit (rt_scene_commit_ex)
     rt_rebuild_detail last_detail{};                  // ... and which builder made the tree (rt_scene_last_rebuild_detail)
+    AllocGate gate;                                   // the device allocations of a commit (armed by commit_impl only)
+    // A commit that failed on the device after it began to write left the scene in no pose at all:
+    // from then on every call that reads or writes the scene returns RT_ERR_DEVICE (scene_lost);
+    // rt_scene_destroy and the last_* getters still work.  Set under the scene lock, never cleared.
+    std::atomic<bool> lost{false};
 };
+// The check every entry point that renders, queries, commits or reads the scene back makes first
+static int32_t scene_lost(const rt_scene* s) {
+    if (!s->lost.load()) return RT_OK;
+    return fail(RT_ERR_DEVICE, "the scene was lost: an earlier rt_scene_commit failed on the device after it began to "
+                               "change the scene (rt_scene_destroy it and create it again)");
+}
 
 static int64_t full_scratch_bytes(const FullScratch& f) {
     return f.cap_px * 16 + f.hitlog_cap * (int64_t)sizeof(DHitRec) +
@@ -1729,6 +1758,7 @@ static double deep_bytes_per_chunk(int32_t max_depth, int32_t width) {
     return lanes * (double)std::max(0, max_depth - kMaxDepthGPU) * (double)sizeof(dev::Frame);
 }
 static int32_t check_renderable(const rt_scene* s, int32_t cam) {
+    if (const int32_t rc = scene_lost(s)) return rc;
     const HostScene& S = s->host;
     if (cam < 0 || cam >= (int32_t)S.cams.size()) return fail(RT_ERR_INVALID_CAMERA, "Invalid camera index");
     // trace() levels beyond kMaxDepthGPU live in a device buffer, one Frame per level and lane
@@ -3412,6 +3442,7 @@ int32_t rt_debug_wide_read(rt_scene* s, int32_t slot, rt_wide_dump* io) {
     if (!io) return fail(RT_ERR_INVALID_ARG, "NULL argument");
     if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
     std::lock_guard<std::mutex> lock(s->mu);
+    if (const int32_t rc = scene_lost(s)) return rc;
     if (scene_busy(s)) return fail(RT_ERR_BUSY, "renders of the scene are in flight: wait for them first");
     try {
         const HostScene& S = s->host;
@@ -3490,6 +3521,7 @@ static bool on_device(const void* p, int device) {
 static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, const rt_hit_batch* hits,
                           uint8_t* occ, bool occluded, const rt_query_bounds* declared, uint32_t flags, void* stream_) {
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (const int32_t rc = scene_lost(s)) return rc;
     if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
     if (flags & ~RT_QUERY_DEVICE) return fail(RT_ERR_INVALID_ARG, "unknown flags");
     if (n < 0 || (n > 0 && (!rays || !rays->origin || !rays->dir))) return fail(RT_ERR_INVALID_ARG, "bad ray arrays");

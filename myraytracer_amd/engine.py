@@ -174,8 +174,9 @@ class RayTracerEngine:
         _check(load_library().rt_scene_set_option(self._h, name.encode(), int(value)))
 
     def set_unsafe_option(self, name: str, value: int):
-        """Test hooks (debug_fail_replica, wide_delta_scale) through the non-production
-        rt_scene_set_unsafe_option; set_option refuses them."""
+        """Test hooks (debug_fail_replica, wide_delta_scale, debug_fail_commit_alloc,
+        debug_fail_commit_step, ...) through the non-production rt_scene_set_unsafe_option;
+        set_option refuses them."""
         _check(load_library().rt_scene_set_unsafe_option(self._h, name.encode(), int(value)))
 
     def get_option(self, name: str) -> int:
@@ -215,7 +216,14 @@ class RayTracerEngine:
         With `rebuild` the flattened instance tree is then built again on the device for the new
         pose (rt_scene_commit_ex): True takes the Morton builder (RT_COMMIT_REBUILD_FIT),
         "clustered" the clustered one (RT_COMMIT_REBUILD_FIT_CLUSTERED); last_rebuild_stats() and
-        last_rebuild_detail() say what happened."""
+        last_rebuild_detail() say what happened.
+        How it ends (rtcore.h "how a commit ends"): a RenderError with RT_ERR_INVALID_ARG or RT_ERR_OOM
+        changed nothing - what was staged is dropped, the last_*_stats() keep the last successful
+        commit's, and self.scene (which follows staging) describes a pose the engine never took.
+        Without memory for the rebuild the pose is committed and the old tree refit:
+        last_rebuild_stats().reason == RT_REBUILD_NO_MEMORY.  A RenderError with RT_ERR_DEVICE means
+        the scene is lost: every later render, submit, query, commit, fit_cost and wide_read of this
+        engine raises RT_ERR_DEVICE; close() it and build a new one."""
         st = A.rt_commit_stats()
         lib = load_library()
         if isinstance(rebuild, str):

@@ -118,10 +118,15 @@ def large_deformable_mesh(devices, snap):
     bad = new.copy()
     bad[-1, 2] = np.nan
     eng.set_positions(0, bad, mirror=False)
+    last = [eng.last_deform_stats(), eng.last_rebuild_stats(), eng.last_rebuild_detail(), eng.last_visibility_stats()]
     with pytest.raises(M.RenderError) as e:
         eng.commit()
     assert e.value.code == A.RT_ERR_INVALID_ARG
     snap("deformed", eng)                                            # the refused commit changed nothing
+    now = [eng.last_deform_stats(), eng.last_rebuild_stats(), eng.last_rebuild_detail(), eng.last_visibility_stats()]
+    for a, b in zip(last, now):                                      # ... nor what the last successful one reports
+        assert [getattr(a, f) for f, _ in a._fields_] == [getattr(b, f) for f, _ in b._fields_], type(a).__name__
+    assert now[0].meshes_deformed == 1
     eng.close()
 
 

@@ -268,6 +268,33 @@ static int run_gpu() {
                    "in-flight render %d counts", k);
         }
     }
+    {   // a commit that runs out of device memory before it changed anything (rtcore.h "how a commit
+        // ends", outcome 2; the test hook fails its first allocation): RT_ERR_OOM, the old pose
+        // still renders, the staging was dropped, and the same commit then succeeds
+        SceneData s;
+        scene_c1(s, 96, 64);
+        myrt::RayTracerEngine eng(s.desc, {0}, {}, true);
+        double m[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0.25, 0, 0, 1};
+        try {
+            eng.setOption("debug_fail_commit_alloc", 1);
+            EXPECT(false, "a test hook was accepted by setOption");
+        } catch (const myrt::RenderError& e) {
+            EXPECT(e.code == RT_ERR_INVALID_ARG, "hook through setOption: code %d", e.code);
+        }
+        eng.setUnsafeOption("debug_fail_commit_alloc", 1);
+        eng.setTransform(0, m);
+        try {
+            eng.commit();
+            EXPECT(false, "the commit did not meet the injected allocation failure");
+        } catch (const myrt::RenderError& e) {
+            EXPECT(e.code == RT_ERR_OOM, "commit without memory: code %d (%s)", e.code, e.what());
+        }
+        EXPECT(eng.option("debug_fail_commit_alloc") == 0, "the hook did not clear itself");
+        compare_with_oracle(s.desc, eng.render(myrt::SceneFormat::Auto, 0), 0, "c1 after a commit without memory");
+        EXPECT(eng.commit().instances_moved == 0, "the staging of the failed commit was kept");
+        eng.setTransform(0, m);
+        EXPECT(eng.commit().instances_moved == 1, "the commit after the failed one");
+    }
     {   // a scene file decoded by the library (RayTracerEngine.init(data:)) renders like its descriptor
         auto eng = myrt::RayTracerEngine::fromData(kC1Json, myrt::SceneFormat::Json);
         auto r = eng.render(myrt::SceneFormat::Auto, 0);
