@@ -296,6 +296,40 @@ public:
         check(rt_query_stats(scene_, slot, &st));
         return st;
     }
+    /* First-hit buffers (rtcore.h "first-hit buffers"): per pixel of the selected chunks the first
+     * primary ray the render casts through it (WantRays: origins, dirs xyz triples, tmin, time) and
+     * the record queryClosest returns for that ray (`want` as for queryClosest), rows packed in chunk
+     * order, `rows` x `width` pixels.  `flags`: RT_GBUFFER_PIXEL_CENTRE (host arrays only here). */
+    struct FirstHits {
+        int32_t rows = 0, width = 0;
+        std::vector<double> origins, dirs, tmin, time;
+        RayHits hits;
+    };
+    enum : uint32_t { WantRays = 64 };
+    FirstHits firstHits(int32_t cameraIndex = 0, int32_t chunkFirst = 0, int32_t chunkStep = 1,
+                        uint32_t want = WantRays | WantT | WantIds, uint32_t flags = 0u, int32_t slot = 0) {
+        FirstHits f;
+        if (cameraIndex >= 0 && cameraIndex < (int32_t)cams_.size()) {
+            f.width = std::max<int32_t>(1, cams_[(size_t)cameraIndex].width);
+            f.rows = rt_rows_for_chunks(cams_[(size_t)cameraIndex].height, chunkFirst, chunkStep);
+        }
+        const size_t n = (size_t)f.rows * (size_t)f.width;
+        rt_gbuffer g{};
+        if (want & WantRays) {
+            f.origins.resize(3 * n); f.dirs.resize(3 * n); f.tmin.resize(n); f.time.resize(n);
+            g.origin = f.origins.data(); g.dir = f.dirs.data(); g.tmin = f.tmin.data(); g.time = f.time.data();
+        }
+        RayHits& h = f.hits;
+        if (want & WantT) { h.t.resize(n); g.hits.t = h.t.data(); }
+        if (want & WantUV) { h.uv.resize(2 * n); g.hits.uv = h.uv.data(); }
+        if (want & WantIds) { h.ids.resize(4 * n); g.hits.ids = h.ids.data(); }
+        if (want & WantPoint) { h.point.resize(3 * n); g.hits.point = h.point.data(); }
+        if (want & WantNormal) { h.normal.resize(3 * n); g.hits.normal = h.normal.data(); }
+        if (want & WantFlags) { h.flags.resize(n); g.hits.flags = h.flags.data(); }
+        check(rt_render_gbuffer(scene_, slot, cameraIndex, chunkFirst, chunkStep, &g,
+                                flags & RT_GBUFFER_PIXEL_CENTRE, nullptr));
+        return f;
+    }
     /* Instance.worldBounds of an instance (any scene), as of the last commit. */
     void instanceBounds(int32_t instance, double lo[3], double hi[3]) const {
         check(rt_scene_instance_bounds(scene_, instance, lo, hi));

@@ -57,7 +57,8 @@
  *      them by symbol): deforming meshes - RT_SCENE_DEFORMABLE, rt_scene_mesh_vertex_count,
  *      rt_scene_set_mesh_positions, rt_scene_last_deform_stats; ray queries - rt_query_closest,
  *      rt_query_occluded, rt_query_stats; the flattened instance tree rebuilt at a commit -
- *      rt_scene_commit_ex with RT_COMMIT_REBUILD_FIT, rt_scene_last_rebuild_stats. */
+ *      rt_scene_commit_ex with RT_COMMIT_REBUILD_FIT, rt_scene_last_rebuild_stats; first-hit
+ *      buffers - rt_render_gbuffer. */
 #define RT_ABI_VERSION 5
 
 #ifdef __cplusplus
@@ -471,6 +472,8 @@ int32_t rt_scene_last_visibility_stats(const rt_scene* scene, rt_visibility_stat
  *   queue_tail (2)       compacted bounce render: levels >= this one traced depth-first in one
  *                        launch (render.hip k_bounce_tail); 0 = one launch per level
  *   query_batch (4194304)  ray queries: rays per launch and per host staging pass (64 .. 2^30)
+ *   gbuffer_tiles (1)    rt_render_gbuffer on device arrays: 1 = the render's 8x8 tiles per wave,
+ *                        0 = 64 consecutive pixels of a row per wave (the results are the same)
  * Unknown names and out-of-range values return RT_ERR_INVALID_ARG.  Set options between
  * renders (not while renders of the scene are in flight).  The test hooks below are refused
  * here (RT_ERR_INVALID_ARG); rt_scene_get_option reads every option. */
@@ -819,6 +822,58 @@ typedef struct rt_query_tables {
     int32_t *inst_object;                        /* per instance */
 } rt_query_tables;
 int32_t rt_debug_query_tables(const rt_scene_desc* desc, uint32_t flags, rt_query_tables* io);
+
+/* ---- first-hit buffers --------------------------------------------
+ * Per pixel of the selected chunks: the first primary ray the render casts through that pixel, and
+ * the record rt_query_closest returns for that ray (picking, depth / id / normal buffers, a correct
+ * ray set for the ray queries).  Added without moving RT_ABI_VERSION: detect the entry point by
+ * symbol, as the ray queries are.
+ *
+ * A pixel's first ray is sample (sx, sy) = (0, 0) of Object+Extension.swift:285-356 exactly as the
+ * render forms it: the pixel's PCG32, two draws for the jitter in sub-cell (0, 0) of the
+ * n x n = floor(sqrt(numSamples))^2 grid, the lens draw when apertureSize > 0 and focusDistance > 0,
+ * one draw for `time`, and tmin = max(distance to the image plane, 0).  For a camera with one sample
+ * it is the pixel's only ray.  Samples after the first are NOT available: their draws follow the
+ * draws shading consumes.  With RT_GBUFFER_PIXEL_CENTRE the ray is the deterministic one through
+ * (i + 0.5, j + 0.5): no lens offset, time = 0, the same tmin formula, nothing drawn.
+ * The record is rt_query_closest's of that ray with its tmin and time (rt_hit_batch above), bit for
+ * bit: the same walk (the one the scene's options select for the render), the scene as of the last
+ * commit.  A ray with a non-finite component (a degenerate camera) is not traced: a miss flagged
+ * RT_HIT_NON_FINITE.
+ *
+ *   layout    chunks are selected and rows packed as by rt_render: chunk c covers rows
+ *             [8c, min(8c + 8, H)), packed in chunk order, rt_rows_for_chunks rows of W pixels.  With
+ *             RT_GBUFFER_FRAME_LAYOUT every array is a whole W x H array and the selected rows are
+ *             written at their image rows (as RT_RENDER_FRAME_LAYOUT); other rows are not touched.
+ *   arrays    without RT_GBUFFER_DEVICE host arrays, staged through the slot's query scratch in
+ *             passes of at most query_batch pixels; the call returns with the results in them.  With
+ *             it every pointer is a device pointer on the slot's device (else RT_ERR_UNSUPPORTED), the
+ *             work is enqueued on `stream` (a hipStream_t, NULL = default) and nothing synchronises:
+ *             the constants are the render's of that camera, so nothing is reduced or read back.
+ *             When no pointer of `hits` is set a small kernel writes the rays alone.  A call with
+ *             every pointer NULL returns RT_OK and launches nothing.
+ *   ids       asking for them uploads the face table on first use, exactly as a query does.
+ *   stats     the call counts as the slot's last query for rt_query_stats: rays = pixels,
+ *             reduced = 0, walk, hits, non_finite, and bounds = the camera's (the largest lens
+ *             origin's reach and coordinate, |d| <= 1 + 2^-50): they may be declared to a query of the
+ *             exported rays.  It shares the slot's query scratch and the queries' ordering rule.
+ *
+ * Refusals (nothing enqueued, outputs untouched): RT_ERR_NO_SCENE; RT_ERR_DEVICE after a failed
+ * commit (the scene was lost); RT_ERR_INVALID_CAMERA; RT_ERR_INVALID_ARG for a bad slot, unknown
+ * flag bits, out == NULL, chunk_first < 0 or chunk_step < 1; RT_ERR_UNSUPPORTED for a pointer that
+ * is not on the slot's device under RT_GBUFFER_DEVICE.  Render option gbuffer_tiles (1) picks the
+ * pixel-to-lane mapping of a device call; the results do not depend on it. */
+typedef struct rt_gbuffer {      /* every pointer optional (NULL = not written) */
+    double *origin, *dir;        /* 3 per pixel: the first ray; same layout as rt_ray_batch */
+    double *tmin, *time;         /* 1 per pixel */
+    rt_hit_batch hits;           /* the record of that ray, as rt_query_closest writes it */
+} rt_gbuffer;
+#define RT_GBUFFER_DEVICE        1u  /* device pointers on the slot's device; enqueue on `stream`, no sync */
+#define RT_GBUFFER_PIXEL_CENTRE  2u
+#define RT_GBUFFER_FRAME_LAYOUT  4u  /* whole W x H arrays, rows written at their image rows (as RT_RENDER_FRAME_LAYOUT) */
+int32_t rt_render_gbuffer(rt_scene* scene, int32_t device_slot, int32_t camera_index,
+                          int32_t chunk_first, int32_t chunk_step,
+                          const rt_gbuffer* out, uint32_t flags, void* stream);
 
 #ifdef __cplusplus
 }

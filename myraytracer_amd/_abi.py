@@ -216,6 +216,17 @@ class rt_query_tables(C.Structure):
 
 QUERY_SYMBOLS = ["rt_query_closest", "rt_query_occluded", "rt_query_stats", "rt_debug_query_tables"]
 
+# ---- first-hit buffers (rtcore.h "first-hit buffers"; appended under ABI 5: detected by symbol) ----
+RT_GBUFFER_DEVICE, RT_GBUFFER_PIXEL_CENTRE, RT_GBUFFER_FRAME_LAYOUT = 1, 2, 4
+
+
+class rt_gbuffer(C.Structure):
+    _fields_ = [("origin", C.c_void_p), ("dir", C.c_void_p), ("tmin", C.c_void_p), ("time", C.c_void_p),
+                ("hits", rt_hit_batch)]
+
+
+GBUFFER_SYMBOLS = ["rt_render_gbuffer"]
+
 RT_MAT = {"": 0, "default": 0, "mirror": 1, "dielectric": 2, "conductor": 3}
 RT_CAM_LOOKAT, RT_CAM_NEARPLANE = 0, 1
 RT_OBJ_MESH, RT_OBJ_TRIANGLE, RT_OBJ_SPHERE, RT_OBJ_PLANE, RT_OBJ_MESH_INSTANCE = 0, 1, 2, 3, 4
@@ -238,6 +249,7 @@ EXPORTED_SYMBOLS = [
     "rt_scene_commit_ex", "rt_scene_last_rebuild_stats",
     *REBUILD_DETAIL_SYMBOLS,
     *VISIBILITY_SYMBOLS,
+    *GBUFFER_SYMBOLS,
 ]
 RT_ABI_VERSION = 5
 
@@ -381,4 +393,8 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.rt_query_stats.restype = C.c_int32
         lib.rt_debug_query_tables.argtypes = [P(rt_scene_desc), C.c_uint32, P(rt_query_tables)]
         lib.rt_debug_query_tables.restype = C.c_int32
+    if hasattr(lib, "rt_render_gbuffer"):   # first-hit buffers (appended under ABI 5: detected by symbol)
+        lib.rt_render_gbuffer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(rt_gbuffer),
+                                          C.c_uint32, C.c_void_p]
+        lib.rt_render_gbuffer.restype = C.c_int32
     return lib

@@ -66,6 +66,33 @@ __device__ __forceinline__ void query_count(const QueryBatch& B, bool hit, uint3
     }
 }
 
+// The record of one traced ray, written at index i of the batch's outputs (each NULL = not written):
+// shared by k_query_closest and k_gbuffer (gbuffer.h), whose records are the same by construction.
+__device__ __forceinline__ void query_record(const RenderParams& P, const QueryBatch& B, size_t i, const V3& o,
+                                             const V3& d, double time, const Hit& h, bool hit, uint32_t cls, Counts& c) {
+    const size_t i3 = 3 * i;
+    if (B.t) B.t[i] = hit ? h.t : DINF;
+    if (B.uv) {
+        const bool tri = hit && P.insts[h.inst].kind == kPrimTriangles;
+        B.uv[2 * i] = tri ? h.u : 0.0;
+        B.uv[2 * i + 1] = tri ? h.v : 0.0;
+    }
+    if (B.ids) {
+        int32_t* q = B.ids + 4 * i;
+        q[0] = hit ? B.inst_obj[h.inst] : -1;
+        q[1] = hit ? B.face[h.tri] : -1;
+        q[2] = hit ? h.inst : -1;
+        q[3] = hit ? P.insts[h.inst].material : -1;
+    }
+    if (B.point || B.normal) {
+        V3 p = v3(0, 0, 0), n = v3(0, 0, 0);
+        if (hit) hit_geometry<false>(P, o, d, time, h, p, n, c);
+        if (B.point) { B.point[i3] = p.x; B.point[i3 + 1] = p.y; B.point[i3 + 2] = p.z; }
+        if (B.normal) { B.normal[i3] = n.x; B.normal[i3 + 1] = n.y; B.normal[i3 + 2] = n.z; }
+    }
+    if (B.flags) B.flags[i] = (uint8_t)((hit ? RT_HIT_VALID : 0u) | cls);
+}
+
 // One-wave blocks, as the render kernels (render.hip kRenderBlock): a block's LDS stack slab is
 // released when its slowest wave ends, and walk lengths of unrelated rays vary widely.
 template <int WALK>
@@ -89,26 +116,7 @@ __global__ __launch_bounds__(64) void k_query_closest(RenderParams P, QueryBatch
             else walk_closest<false, WALK>(P, o, d, rcp(d), tlo, time, h, st, c);
         }
         hit = h.inst >= 0;
-        if (B.t) B.t[i] = hit ? h.t : DINF;
-        if (B.uv) {
-            const bool tri = hit && P.insts[h.inst].kind == kPrimTriangles;
-            B.uv[2 * (size_t)i] = tri ? h.u : 0.0;
-            B.uv[2 * (size_t)i + 1] = tri ? h.v : 0.0;
-        }
-        if (B.ids) {
-            int32_t* q = B.ids + 4 * (size_t)i;
-            q[0] = hit ? B.inst_obj[h.inst] : -1;
-            q[1] = hit ? B.face[h.tri] : -1;
-            q[2] = hit ? h.inst : -1;
-            q[3] = hit ? P.insts[h.inst].material : -1;
-        }
-        if (B.point || B.normal) {
-            V3 p = v3(0, 0, 0), n = v3(0, 0, 0);
-            if (hit) hit_geometry<false>(P, o, d, time, h, p, n, c);
-            if (B.point) { B.point[i3] = p.x; B.point[i3 + 1] = p.y; B.point[i3 + 2] = p.z; }
-            if (B.normal) { B.normal[i3] = n.x; B.normal[i3 + 1] = n.y; B.normal[i3 + 2] = n.z; }
-        }
-        if (B.flags) B.flags[i] = (uint8_t)((hit ? RT_HIT_VALID : 0u) | cls);
+        query_record(P, B, (size_t)i, o, d, time, h, hit, cls, c);
     }
     query_count(B, hit, cls);
 }

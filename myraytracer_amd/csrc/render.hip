@@ -1138,6 +1138,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MYRT_SHADE_W
 }  // namespace myrt
 
 #include "query.h"
+#include "gbuffer.h"
 
 // ================================================================== host side / C ABI
 using namespace myrt;
@@ -1369,6 +1370,7 @@ enum OptId {
     kOptDeepCapMb, kOptBatches, kOptZerocopy, kOptSubmitEvents, kOptSubmitCounters, kOptSubmitDma,
     kOptDebugFailReplica, kOptWideDeltaScale, kOptNodeLists, kOptTileOrder, kOptFit, kOptQueueTail, kOptQueryBatch,
     kOptRebuildDepthCap, kOptRebuildClusterIterCap, kOptDebugFailCommitAlloc, kOptDebugFailCommitStep,
+    kOptGBufferTiles,
     kOptCount
 };
 // `unsafe` options are test hooks: rt_scene_set_option refuses them (RT_ERR_INVALID_ARG); only the
@@ -1414,6 +1416,8 @@ static const OptDef kOptDefs[kOptCount] = {
     {"debug_fail_commit_step", 0, 0, 10, true},         // test hook: the next commit returns as for a HIP error before its step k
                                                         // (commit_impl's steps 1 .. 9 in order, 10 the rebuild); 0 = off.  Both are
                                                         // read by commit_impl only and cleared when that commit returns
+    {"gbuffer_tiles", 1, 0, 1},           // rt_render_gbuffer on device arrays: 1 = the render's 8x8 tiles in xcd_tile order,
+                                          // 0 = 64 consecutive pixels of a row per wave (tools/probe_gbuffer.py)
 };
 
 struct rt_scene {
@@ -3518,6 +3522,27 @@ static bool on_device(const void* p, int device) {
     return at.type == hipMemoryTypeDevice && at.device == device;
 }
 
+// The slot's query scratch, under the scene's lock: the query words and their pinned copy, the face
+// table on the first call that asks for ids, and staging for `stage` rays of a host-array call.
+static int32_t query_scratch(const HostScene& S, DeviceReplica& r, bool ids, int64_t stage) {
+    if (!r.q_words) HIP_TRY(hipMalloc((void**)&r.q_words, dev::kQWords * 8));
+    if (!r.q_host) HIP_TRY(hipHostMalloc((void**)&r.q_host, dev::kQWords * 8, hipHostMallocDefault));
+    if (ids && !r.q_face) {
+        int64_t bytes = 0;
+        int32_t rc = upload(S.face, &r.q_face, bytes);
+        if (rc == RT_OK) rc = upload(S.inst_obj, &r.q_inst_obj, bytes);
+        if (rc != RT_OK) {
+            (void)hipFree(r.q_face); (void)hipFree(r.q_inst_obj);
+            r.q_face = nullptr; r.q_inst_obj = nullptr;
+            return rc;
+        }
+        r.bytes += (int64_t)(S.face.size() + S.inst_obj.size()) * 4;
+    }
+    if (stage > 0 && !grow_buf(r, &r.q_buf, r.q_cap, stage * kQueryStageBytes, 1))
+        return fail(RT_ERR_OOM, "query staging does not fit on the device");
+    return RT_OK;
+}
+
 static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, const rt_hit_batch* hits,
                           uint8_t* occ, bool occluded, const rt_query_bounds* declared, uint32_t flags, void* stream_) {
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
@@ -3553,21 +3578,7 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
         P = make_params(s, r, 0, 0, 1, nullptr, nullptr);
         batch = s->opt[kOptQueryBatch];
         for (int k = 0; k < 3; ++k) center[k] = S.scene_center[k];
-        if (!r.q_words) HIP_TRY(hipMalloc((void**)&r.q_words, dev::kQWords * 8));
-        if (!r.q_host) HIP_TRY(hipHostMalloc((void**)&r.q_host, dev::kQWords * 8, hipHostMallocDefault));
-        if (H.ids && !r.q_face) {     // the face table, on the first query that asks for ids
-            int64_t bytes = 0;
-            int32_t rc = upload(S.face, &r.q_face, bytes);
-            if (rc == RT_OK) rc = upload(S.inst_obj, &r.q_inst_obj, bytes);
-            if (rc != RT_OK) {
-                (void)hipFree(r.q_face); (void)hipFree(r.q_inst_obj);
-                r.q_face = nullptr; r.q_inst_obj = nullptr;
-                return rc;
-            }
-            r.bytes += (int64_t)(S.face.size() + S.inst_obj.size()) * 4;
-        }
-        if (!on_dev && !grow_buf(r, &r.q_buf, r.q_cap, std::min(n, batch) * kQueryStageBytes, 1))
-            return fail(RT_ERR_OOM, "query staging does not fit on the device");
+        if (const int32_t rc = query_scratch(S, r, H.ids != nullptr, on_dev ? 0 : std::min(n, batch))) return rc;
     }
     const int64_t m_max = std::min(n, batch);
     const int64_t launches = (n + batch - 1) / batch;
@@ -3667,6 +3678,131 @@ int32_t rt_query_closest(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batc
 int32_t rt_query_occluded(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, uint8_t* out,
                           const rt_query_bounds* declared, uint32_t flags, void* stream) {
     return query_impl(s, slot, n, rays, nullptr, out, true, declared, flags, stream);
+}
+
+// ---- first-hit buffers (rtcore.h "first-hit buffers"; gbuffer.h) -----------------------
+// The constants are the render's of that camera (make_params), so nothing is reduced and nothing is
+// read back: a device call only enqueues.  A host-array call is staged through the slot's query
+// scratch (query_stage: the ray in o / d / tlim / time, the record in the rest) in passes of at most
+// query_batch pixels of the packed selection, each pass copied out before the next reuses the staging.
+int32_t rt_render_gbuffer(rt_scene* s, int32_t slot, int32_t cam, int32_t first, int32_t step, const rt_gbuffer* out,
+                          uint32_t flags, void* stream_) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (const int32_t rc = scene_lost(s)) return rc;
+    const HostScene& S = s->host;
+    if (cam < 0 || cam >= (int32_t)S.cams.size()) return fail(RT_ERR_INVALID_CAMERA, "Invalid camera index");
+    if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
+    if (flags & ~(uint32_t)(RT_GBUFFER_DEVICE | RT_GBUFFER_PIXEL_CENTRE | RT_GBUFFER_FRAME_LAYOUT))
+        return fail(RT_ERR_INVALID_ARG, "unknown flags");
+    if (!out) return fail(RT_ERR_INVALID_ARG, "out is NULL");
+    if (first < 0 || step < 1) return fail(RT_ERR_INVALID_ARG, "bad chunk selection");
+    const rt_gbuffer O = *out;
+    const rt_hit_batch& H = O.hits;
+    const bool on_dev = (flags & RT_GBUFFER_DEVICE) != 0, frame = (flags & RT_GBUFFER_FRAME_LAYOUT) != 0;
+    const bool record = H.t || H.uv || H.ids || H.point || H.normal || H.flags;
+    if (!record && !O.origin && !O.dir && !O.tmin && !O.time) return RT_OK;      // nothing asked for
+    DeviceReplica& r = s->devs[slot];
+    if (on_dev)
+        for (const void* p : {(const void*)O.origin, (const void*)O.dir, (const void*)O.tmin, (const void*)O.time,
+                              (const void*)H.t, (const void*)H.uv, (const void*)H.ids, (const void*)H.point,
+                              (const void*)H.normal, (const void*)H.flags})
+            if (p && !on_device(p, r.device))
+                return fail(RT_ERR_UNSUPPORTED, "RT_GBUFFER_DEVICE: not a device pointer on the slot's device");
+    hipStream_t stream = (hipStream_t)stream_;
+    RenderParams P;
+    int64_t batch = 0, n = 0;
+    int walk = 0;
+    bool tiles = false;
+    {   // prepared under the scene's lock: the render's constants of this camera, the slot's query scratch
+        std::lock_guard<std::mutex> lock(s->mu);
+        HIP_TRY(hipSetDevice(r.device));
+        P = make_params(s, r, cam, first, step, nullptr, nullptr);
+        if (frame) { P.out_first = 0; P.out_step = 1; }
+        n = (int64_t)rt_rows_for_chunks(P.cam.height, first, step) * P.cam.width;
+        if (n == 0) { r.q_last = rt_query_counts{}; return RT_OK; }        // no chunk selected
+        if (n > INT32_MAX) return fail(RT_ERR_UNSUPPORTED, "more than 2^31 - 1 pixels selected");
+        batch = s->opt[kOptQueryBatch];
+        tiles = s->opt[kOptGBufferTiles] != 0;
+        if (const int32_t rc = query_scratch(S, r, H.ids != nullptr, on_dev ? 0 : std::min(n, batch))) return rc;
+        walk = select_walk(s, P, false);      // the render kernels' walk
+        const rt_camera& c = S.cams[cam];
+        const double ce[3] = {c.position.x, c.position.y, c.position.z}, lens = std::fabs(c.aperture_size);
+        r.q_last = rt_query_counts{};
+        r.q_last.rays = n; r.q_last.launches = on_dev ? 1 : (n + batch - 1) / batch; r.q_last.reduced = 0;
+        r.q_last.walk = walk;
+        // the camera's bounds, as make_params hands them to set_ray_bounds (directions are normalised:
+        // |d| <= 1 + 2^-50), so they can be declared to a query of the exported rays
+        r.q_last.bounds = rt_query_bounds{dist_to_center(S, ce) + lens,
+                                          std::max({std::fabs(ce[0]), std::fabs(ce[1]), std::fabs(ce[2])}) + lens,
+                                          1.0 + 0x1p-50};
+    }
+    HIP_TRY(hipMemsetAsync(r.q_words, 0, dev::kQWords * 8, stream));
+    dev::QueryBatch B{};
+    B.words = r.q_words; B.face = r.q_face; B.inst_obj = r.q_inst_obj;
+    dev::GBufferBatch G{};
+    G.centre = (flags & RT_GBUFFER_PIXEL_CENTRE) ? 1u : 0u;
+    const size_t lds = (size_t)dev::kLds * kRenderBlock * sizeof(unsigned long long);
+#define MYRT_GBUF(W_) hipLaunchKernelGGL((dev::k_gbuffer<W_>), grid, dim3(kRenderBlock), lds, stream, P, B, G)
+    auto launch_rays = [&]() {
+        const dim3 grid((unsigned)((G.n + dev::kGBufferRaysBlock - 1) / dev::kGBufferRaysBlock));
+        hipLaunchKernelGGL(dev::k_gbuffer_rays, grid, dim3(dev::kGBufferRaysBlock), 0, stream, P, G);
+    };
+    if (on_dev) {
+        G.o = O.origin; G.d = O.dir; G.tmin = O.tmin; G.time = O.time;
+        B.t = H.t; B.uv = H.uv; B.ids = H.ids; B.point = H.point; B.normal = H.normal; B.flags = H.flags;
+        G.first = 0; G.n = (int32_t)n; G.staged = 0;
+        if (!record) {
+            launch_rays();
+        } else {
+            G.tiles = tiles ? 1 : 0;
+            const dim3 grid = tiles ? render_grid(P, kRenderBlock, dev::kTileW)
+                                    : dim3((unsigned)((n + kRenderBlock - 1) / kRenderBlock));
+            MYRT_BY_WALK(MYRT_GBUF);
+        }
+        HIP_TRY(hipGetLastError());
+        return RT_OK;
+    }
+    const int64_t m_max = std::min(n, batch);
+    const QueryStage st = query_stage(r.q_buf, m_max);
+    const int64_t W = P.cam.width;
+    for (int64_t base = 0; base < n; base += batch) {
+        const int64_t m = std::min(batch, n - base);
+        G.o = O.origin ? st.o : nullptr; G.d = O.dir ? st.d : nullptr;
+        G.tmin = O.tmin ? st.tlim : nullptr; G.time = O.time ? st.time : nullptr;
+        B.t = H.t ? st.t : nullptr; B.uv = H.uv ? st.uv : nullptr; B.ids = H.ids ? st.ids : nullptr;
+        B.point = H.point ? st.point : nullptr; B.normal = H.normal ? st.normal : nullptr;
+        B.flags = H.flags ? st.flags : nullptr;
+        G.tiles = 0; G.staged = 1; G.first = (int32_t)base; G.n = (int32_t)m;
+        if (!record) {
+            launch_rays();
+        } else {
+            const dim3 grid((unsigned)((m + kRenderBlock - 1) / kRenderBlock));
+            MYRT_BY_WALK(MYRT_GBUF);
+        }
+        HIP_TRY(hipGetLastError());
+        // the pass's pixels [base, base + m) of the packed selection, in runs that are contiguous in the
+        // caller's arrays: the whole pass, or with the frame layout one run per chunk (8 W pixels)
+        for (int64_t p0 = base; p0 < base + m;) {
+            const int64_t slot_rows = frame ? (p0 / (8 * W) + 1) * 8 * W : base + m;
+            const int64_t p1 = std::min(base + m, slot_rows), k = p1 - p0, src = p0 - base;
+            const int64_t row = p0 / W;
+            const int64_t dst = frame ? (((int64_t)first + (row >> 3) * step) * 8 + (row & 7)) * W + (p0 - row * W) : p0;
+            const auto back = [&](void* to, const void* from, size_t elem) {
+                return to ? hipMemcpyAsync((char*)to + (size_t)dst * elem, (const char*)from + (size_t)src * elem,
+                                           (size_t)k * elem, hipMemcpyDeviceToHost, stream)
+                          : hipSuccess;
+            };
+            HIP_TRY(back(O.origin, st.o, 24)); HIP_TRY(back(O.dir, st.d, 24));
+            HIP_TRY(back(O.tmin, st.tlim, 8)); HIP_TRY(back(O.time, st.time, 8));
+            HIP_TRY(back(H.t, st.t, 8)); HIP_TRY(back(H.uv, st.uv, 16)); HIP_TRY(back(H.ids, st.ids, 16));
+            HIP_TRY(back(H.point, st.point, 24)); HIP_TRY(back(H.normal, st.normal, 24));
+            HIP_TRY(back(H.flags, st.flags, 1));
+            p0 = p1;
+        }
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+#undef MYRT_GBUF
+    return RT_OK;
 }
 #undef MYRT_BY_WALK
 

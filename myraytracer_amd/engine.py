@@ -656,6 +656,52 @@ class RayTracerEngine:
         _check(load_library().rt_query_stats(self._h, int(slot), C.byref(st)))
         return st
 
+    # -- first-hit buffers (rt_render_gbuffer)
+    def first_hits(self, camera_index: int = 0, chunk_first: int = 0, chunk_step: int = 1, *,
+                   want=("rays", "t", "ids"), centre: bool = False, frame_layout: bool = False, slot: int = 0,
+                   out=None) -> "FirstHits":
+        """Per pixel of the selected 8-row chunks, the first primary ray the render casts through it
+        and what that ray hits (rt_render_gbuffer): a FirstHits whose `origins`, `dirs`, `tmin`, `time`
+        are shaped (rows, W[, 3]) and whose `hits` is a RayHits shaped (rows, W[, cols]), exactly what
+        query_closest returns for those rays.  `want` names what to fill: "rays" (all four ray arrays)
+        or any of origins, dirs, tmin, time, and the RayHits fields t, uv, ids, point, normal, flags;
+        the rest is None.  `centre`: the deterministic ray through each pixel's centre (no lens, time 0)
+        instead of the render's jittered one.  Rows are packed in chunk order (rows_for_chunks rows), or
+        with `frame_layout` every array is a whole H x W frame whose unselected rows are not written.
+        numpy arrays come back by default.  `out` = a dict, keyed as `want`, of contiguous float64 /
+        int32 / uint8 torch tensors on the slot's device: they are written in place, enqueued on
+        torch.cuda.current_stream() with no synchronisation, and `want` is ignored."""
+        cam = self.scene.cameras[camera_index] if 0 <= camera_index < len(self.scene.cameras) else None
+        W, H = (max(1, int(cam.image_resolution[0])), max(1, int(cam.image_resolution[1]))) if cam else (0, 0)
+        rows = H if frame_layout else rows_for_chunks(H, chunk_first, chunk_step)
+        fields = dict(FirstHits.RAYS, **RayHits.FIELDS)
+        names = list(out) if out is not None else [f for w in want for f in (FirstHits.RAYS if w == "rays" else (w,))]
+        unknown = set(names) - set(fields)
+        if unknown:
+            raise ValueError(f"unknown FirstHits fields {sorted(unknown)}")
+        on_dev = out is not None
+        res, gb = FirstHits(hits=RayHits(), rows=rows, width=W), A.rt_gbuffer()
+        for name in names:
+            cols, dt = fields[name]
+            shape = (rows, W, cols) if cols > 1 else (rows, W)
+            if on_dev:
+                import torch
+                a = out[name]
+                tdt = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8}[dt]
+                if not isinstance(a, torch.Tensor) or not a.is_cuda or a.dtype != tdt or not a.is_contiguous() or \
+                        a.numel() != rows * W * cols:
+                    raise ValueError(f"{name}: a contiguous {tdt} tensor of {shape} on the slot's device")
+            else:
+                a = np.empty(shape, dt)
+            ray = name in FirstHits.RAYS
+            setattr(res if ray else res.hits, name, a)
+            setattr(gb if ray else gb.hits, FirstHits.ABI.get(name, name), _ptr(a))
+        flags = (A.RT_GBUFFER_DEVICE if on_dev else 0) | (A.RT_GBUFFER_PIXEL_CENTRE if centre else 0) | \
+                (A.RT_GBUFFER_FRAME_LAYOUT if frame_layout else 0)
+        _check(load_library().rt_render_gbuffer(self._h, int(slot), int(camera_index), int(chunk_first),
+                                                int(chunk_step), C.byref(gb), flags, _stream(on_dev)))
+        return res
+
     def bvh_hash(self, instance: int) -> int:
         return int(load_library().rt_debug_bvh_hash(self._h, instance))
 
@@ -760,6 +806,22 @@ class RayHits:
     flags: object = None
     FIELDS = {"t": (1, np.float64), "uv": (2, np.float64), "ids": (4, np.int32), "point": (3, np.float64),
               "normal": (3, np.float64), "flags": (1, np.uint8)}
+
+
+@dataclass
+class FirstHits:
+    """What first_hits returns: per pixel the first primary ray of the render (origins, dirs (rows, W,
+    3); tmin, time (rows, W)) and its record (`hits`, a RayHits of the same leading shape); the
+    fields that were not asked for are None."""
+    origins: object = None
+    dirs: object = None
+    tmin: object = None
+    time: object = None
+    hits: "RayHits" = None
+    rows: int = 0
+    width: int = 0
+    RAYS = {"origins": (3, np.float64), "dirs": (3, np.float64), "tmin": (1, np.float64), "time": (1, np.float64)}
+    ABI = {"origins": "origin", "dirs": "dir"}            # rt_gbuffer's member names
 
 
 def _ptr(a):

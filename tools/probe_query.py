@@ -1,8 +1,9 @@
 """What does a ray query cost, and what is the order of the rays worth?  
 
 C3 (1.02M triangles, the four-wide identity walk), three sets of 2^22 rays:
-  primary   the camera's primary rays in pixel order (the frame's camera, at the resolution that
-            gives 2^22 pixels)
+  primary   the camera's primary rays in pixel order: the rays the render casts, exported by
+            rt_render_gbuffer (the frame's camera, at the resolution that gives 2^22 pixels; the
+            figures of DESIGN.md §11 were measured on pinhole rays through pixel centres)
   shuffled  the same rays in random order
   random    uniformly random origins in the scene box, random directions
 each through rt_query_closest (want t, uv, ids) and rt_query_occluded (tMax = +inf), as:
@@ -19,6 +20,7 @@ median.  Prints text and one JSON line per figure, with the library's sha-256 pr
 usage: probe_query.py [--log2 22] [--reps 7] [--scene c3]
 The probe needs a GPU; nothing falls back."""
 import argparse
+import dataclasses
 import hashlib
 import json
 import os
@@ -31,33 +33,28 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 
-def primary_rays(cam, n):
-    """The first n pinhole rays, in pixel order, of `cam` at the resolution of its aspect that has
-    at least n pixels."""
+def primary_resolution(cam, n):
+    """The resolution of `cam`'s aspect that has at least n pixels."""
     W0, H0 = cam.image_resolution
     k = np.sqrt(n / (W0 * H0))
     W, H = int(np.ceil(W0 * k)), int(np.ceil(H0 * k))
     while W * H < n:
         H += 1
-    eye = np.asarray(cam.position, np.float64)
-    w = np.asarray(cam.gaze_point, np.float64) - eye
-    w /= np.linalg.norm(w)
-    u = np.cross(w, np.asarray(cam.up, np.float64))
-    u /= np.linalg.norm(u)
-    v = np.cross(u, w)
-    hh = np.tan(np.radians(cam.fovy) / 2.0)
-    idx = np.arange(n)
-    x, y = (idx % W + 0.5) / W * 2.0 - 1.0, (idx // W + 0.5) / H * 2.0 - 1.0
-    D = w[None, :] + (x * hh * W / H)[:, None] * u[None, :] - (y * hh)[:, None] * v[None, :]
-    D /= np.linalg.norm(D, axis=1, keepdims=True)
-    return np.ascontiguousarray(np.broadcast_to(eye, (n, 3))), np.ascontiguousarray(D)
+    return W, H
 
 
-def ray_sets(sc, n, seed=5):
+def primary_rays(eng, n):
+    """The first n primary rays the render casts, in pixel order: exported by rt_render_gbuffer
+    (engine.first_hits), not restated here."""
+    fh = eng.first_hits(want=("origins", "dirs"))
+    return (np.ascontiguousarray(fh.origins.reshape(-1, 3)[:n]), np.ascontiguousarray(fh.dirs.reshape(-1, 3)[:n]))
+
+
+def ray_sets(sc, eng, n, seed=5):
     P = np.asarray(sc.objects[0].positions, np.float64)
     lo, hi = P.min(0), P.max(0)
     rng = np.random.RandomState(seed)
-    Oa, Da = primary_rays(sc.cameras[0], n)
+    Oa, Da = primary_rays(eng, n)
     perm = rng.permutation(n)
     Oc = rng.uniform(lo, hi, size=(n, 3))
     Dc = rng.normal(size=(n, 3))
@@ -78,8 +75,9 @@ def main():
     sha = hashlib.sha256(open(M.engine.LIB_PATH, "rb").read()).hexdigest()[:16]
     sc = {"c3": scenes.scene_c3, "c2": scenes.scene_c2}[args.scene](inline=True)
     n = 1 << args.log2
-    sets, (lo, hi) = ray_sets(sc, n)
+    sc.cameras[0] = dataclasses.replace(sc.cameras[0], image_resolution=primary_resolution(sc.cameras[0], n))
     eng = M.RayTracerEngine(sc)
+    sets, (lo, hi) = ray_sets(sc, eng, n)
     centre = 0.5 * (lo + hi)
     print(f"probe_query: {args.scene}, {n} rays per set, {args.reps} reps, libmyrt sha256 {sha}", flush=True)
 
