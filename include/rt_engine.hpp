@@ -226,6 +226,22 @@ public:
         check(rt_scene_last_visibility_stats(scene_, &st));
         return st;
     }
+    /* Ray masks (rtcore.h "ray masks"): setMask gives the instance of scene object `objectIndex` 32
+     * mask bits, applied at once with no commit, on static scenes too; maskOf reads them back.  A ray
+     * of a masked query (queryClosest / queryOccluded with `masks`, firstHitsMasked) sees an instance
+     * iff the two masks share a bit and the instance is visible. */
+    void setMask(int32_t objectIndex, uint32_t mask) {
+        const int32_t k = instanceOf(objectIndex);
+        if (k < 0) throw RenderError(RT_ERR_INVALID_ARG, "the object produced no instance");
+        check(rt_scene_set_instance_masks(scene_, k, 1, &mask));
+    }
+    uint32_t maskOf(int32_t objectIndex) const {
+        const int32_t k = instanceOf(objectIndex);
+        if (k < 0) throw RenderError(RT_ERR_INVALID_ARG, "the object produced no instance");
+        uint32_t m = 0;
+        check(rt_scene_instance_mask(scene_, k, &m));
+        return m;
+    }
     /* Deforming meshes (an engine built with `deformable`, which implies `dynamic`): BVHBuilder.refit
      * (BVH.swift:254-291) applied to a BLAS on the device.  setPositions stages xyz triples (and, for a
      * mesh created with per-vertex normals, optionally new normals) for mesh object `objectIndex`
@@ -259,37 +275,45 @@ public:
                          const std::vector<double>& tmin = {}, const std::vector<double>& time = {},
                          uint32_t want = WantT | WantUV | WantIds, const rt_query_bounds* declared = nullptr,
                          uint32_t flags = 0u, int32_t slot = 0) {
-        const int64_t n = (int64_t)origins.size() / 3;
-        if (dirs.size() != origins.size() || (!tmin.empty() && (int64_t)tmin.size() != n) ||
-            (!time.empty() && (int64_t)time.size() != n))
-            throw RenderError(RT_ERR_INVALID_ARG, "ray arrays differ in length");
-        RayHits h;
-        rt_hit_batch hb{};
-        if (want & WantT) { h.t.resize((size_t)n); hb.t = h.t.data(); }
-        if (want & WantUV) { h.uv.resize(2 * (size_t)n); hb.uv = h.uv.data(); }
-        if (want & WantIds) { h.ids.resize(4 * (size_t)n); hb.ids = h.ids.data(); }
-        if (want & WantPoint) { h.point.resize(3 * (size_t)n); hb.point = h.point.data(); }
-        if (want & WantNormal) { h.normal.resize(3 * (size_t)n); hb.normal = h.normal.data(); }
-        if (want & WantFlags) { h.flags.resize((size_t)n); hb.flags = h.flags.data(); }
-        const rt_ray_batch rb{origins.data(), dirs.data(), tmin.empty() ? nullptr : tmin.data(),
-                              time.empty() ? nullptr : time.data()};
-        check(rt_query_closest(scene_, slot, n, &rb, &hb, declared, flags & ~RT_QUERY_DEVICE, nullptr));
-        return h;
+        return queryClosestWith(nullptr, origins, dirs, tmin, time, want, declared, flags, slot);
+    }
+    /* ... with ray masks: one mask for every ray, or one per ray (rt_query_closest_masked). */
+    RayHits queryClosest(uint32_t mask, const std::vector<double>& origins, const std::vector<double>& dirs,
+                         const std::vector<double>& tmin = {}, const std::vector<double>& time = {},
+                         uint32_t want = WantT | WantUV | WantIds, const rt_query_bounds* declared = nullptr,
+                         uint32_t flags = 0u, int32_t slot = 0) {
+        const rt_ray_masks m{nullptr, mask, 0u};
+        return queryClosestWith(&m, origins, dirs, tmin, time, want, declared, flags, slot);
+    }
+    RayHits queryClosest(const std::vector<uint32_t>& masks, const std::vector<double>& origins,
+                         const std::vector<double>& dirs, const std::vector<double>& tmin = {},
+                         const std::vector<double>& time = {}, uint32_t want = WantT | WantUV | WantIds,
+                         const rt_query_bounds* declared = nullptr, uint32_t flags = 0u, int32_t slot = 0) {
+        if (masks.size() != origins.size() / 3) throw RenderError(RT_ERR_INVALID_ARG, "one mask per ray");
+        const rt_ray_masks m{masks.data(), 0u, 0u};
+        return queryClosestWith(&m, origins, dirs, tmin, time, want, declared, flags, slot);
     }
     /* Per ray 0 = free, 1 = blocked, 2 = not traced (beyond `declared`, or non-finite). */
     std::vector<uint8_t> queryOccluded(const std::vector<double>& origins, const std::vector<double>& dirs,
                                        const std::vector<double>& tmax = {}, const std::vector<double>& time = {},
                                        const rt_query_bounds* declared = nullptr, uint32_t flags = 0u,
                                        int32_t slot = 0) {
-        const int64_t n = (int64_t)origins.size() / 3;
-        if (dirs.size() != origins.size() || (!tmax.empty() && (int64_t)tmax.size() != n) ||
-            (!time.empty() && (int64_t)time.size() != n))
-            throw RenderError(RT_ERR_INVALID_ARG, "ray arrays differ in length");
-        std::vector<uint8_t> out((size_t)n);
-        const rt_ray_batch rb{origins.data(), dirs.data(), tmax.empty() ? nullptr : tmax.data(),
-                              time.empty() ? nullptr : time.data()};
-        check(rt_query_occluded(scene_, slot, n, &rb, out.data(), declared, flags & ~RT_QUERY_DEVICE, nullptr));
-        return out;
+        return queryOccludedWith(nullptr, origins, dirs, tmax, time, declared, flags, slot);
+    }
+    std::vector<uint8_t> queryOccluded(uint32_t mask, const std::vector<double>& origins,
+                                       const std::vector<double>& dirs, const std::vector<double>& tmax = {},
+                                       const std::vector<double>& time = {}, const rt_query_bounds* declared = nullptr,
+                                       uint32_t flags = 0u, int32_t slot = 0) {
+        const rt_ray_masks m{nullptr, mask, 0u};
+        return queryOccludedWith(&m, origins, dirs, tmax, time, declared, flags, slot);
+    }
+    std::vector<uint8_t> queryOccluded(const std::vector<uint32_t>& masks, const std::vector<double>& origins,
+                                       const std::vector<double>& dirs, const std::vector<double>& tmax = {},
+                                       const std::vector<double>& time = {}, const rt_query_bounds* declared = nullptr,
+                                       uint32_t flags = 0u, int32_t slot = 0) {
+        if (masks.size() != origins.size() / 3) throw RenderError(RT_ERR_INVALID_ARG, "one mask per ray");
+        const rt_ray_masks m{masks.data(), 0u, 0u};
+        return queryOccludedWith(&m, origins, dirs, tmax, time, declared, flags, slot);
     }
     rt_query_counts lastQueryStats(int32_t slot = 0) const {
         rt_query_counts st{};
@@ -308,6 +332,59 @@ public:
     enum : uint32_t { WantRays = 64 };
     FirstHits firstHits(int32_t cameraIndex = 0, int32_t chunkFirst = 0, int32_t chunkStep = 1,
                         uint32_t want = WantRays | WantT | WantIds, uint32_t flags = 0u, int32_t slot = 0) {
+        return firstHitsWith(nullptr, cameraIndex, chunkFirst, chunkStep, want, flags, slot);
+    }
+    /* ... with one ray mask for the whole call (rt_render_gbuffer_masked): a camera layer, picking. */
+    FirstHits firstHitsMasked(uint32_t mask, int32_t cameraIndex = 0, int32_t chunkFirst = 0, int32_t chunkStep = 1,
+                              uint32_t want = WantRays | WantT | WantIds, uint32_t flags = 0u, int32_t slot = 0) {
+        return firstHitsWith(&mask, cameraIndex, chunkFirst, chunkStep, want, flags, slot);
+    }
+    /* Instance.worldBounds of an instance (any scene), as of the last commit. */
+    void instanceBounds(int32_t instance, double lo[3], double hi[3]) const {
+        check(rt_scene_instance_bounds(scene_, instance, lo, hi));
+    }
+
+private:
+    /* The bodies of queryClosest / queryOccluded / firstHits and of their masked forms (masks / mask NULL: unmasked). */
+    RayHits queryClosestWith(const rt_ray_masks* masks, const std::vector<double>& origins,
+                             const std::vector<double>& dirs, const std::vector<double>& tmin,
+                             const std::vector<double>& time, uint32_t want, const rt_query_bounds* declared,
+                             uint32_t flags, int32_t slot) {
+        const int64_t n = (int64_t)origins.size() / 3;
+        if (dirs.size() != origins.size() || (!tmin.empty() && (int64_t)tmin.size() != n) ||
+            (!time.empty() && (int64_t)time.size() != n))
+            throw RenderError(RT_ERR_INVALID_ARG, "ray arrays differ in length");
+        RayHits h;
+        rt_hit_batch hb{};
+        if (want & WantT) { h.t.resize((size_t)n); hb.t = h.t.data(); }
+        if (want & WantUV) { h.uv.resize(2 * (size_t)n); hb.uv = h.uv.data(); }
+        if (want & WantIds) { h.ids.resize(4 * (size_t)n); hb.ids = h.ids.data(); }
+        if (want & WantPoint) { h.point.resize(3 * (size_t)n); hb.point = h.point.data(); }
+        if (want & WantNormal) { h.normal.resize(3 * (size_t)n); hb.normal = h.normal.data(); }
+        if (want & WantFlags) { h.flags.resize((size_t)n); hb.flags = h.flags.data(); }
+        const rt_ray_batch rb{origins.data(), dirs.data(), tmin.empty() ? nullptr : tmin.data(),
+                              time.empty() ? nullptr : time.data()};
+        if (masks) check(rt_query_closest_masked(scene_, slot, n, &rb, &hb, declared, flags & ~RT_QUERY_DEVICE, nullptr, masks));
+        else check(rt_query_closest(scene_, slot, n, &rb, &hb, declared, flags & ~RT_QUERY_DEVICE, nullptr));
+        return h;
+    }
+    std::vector<uint8_t> queryOccludedWith(const rt_ray_masks* masks, const std::vector<double>& origins,
+                                           const std::vector<double>& dirs, const std::vector<double>& tmax,
+                                           const std::vector<double>& time, const rt_query_bounds* declared,
+                                           uint32_t flags, int32_t slot) {
+        const int64_t n = (int64_t)origins.size() / 3;
+        if (dirs.size() != origins.size() || (!tmax.empty() && (int64_t)tmax.size() != n) ||
+            (!time.empty() && (int64_t)time.size() != n))
+            throw RenderError(RT_ERR_INVALID_ARG, "ray arrays differ in length");
+        std::vector<uint8_t> out((size_t)n);
+        const rt_ray_batch rb{origins.data(), dirs.data(), tmax.empty() ? nullptr : tmax.data(),
+                              time.empty() ? nullptr : time.data()};
+        if (masks) check(rt_query_occluded_masked(scene_, slot, n, &rb, out.data(), declared, flags & ~RT_QUERY_DEVICE, nullptr, masks));
+        else check(rt_query_occluded(scene_, slot, n, &rb, out.data(), declared, flags & ~RT_QUERY_DEVICE, nullptr));
+        return out;
+    }
+    FirstHits firstHitsWith(const uint32_t* mask, int32_t cameraIndex, int32_t chunkFirst, int32_t chunkStep,
+                            uint32_t want, uint32_t flags, int32_t slot) {
         FirstHits f;
         if (cameraIndex >= 0 && cameraIndex < (int32_t)cams_.size()) {
             f.width = std::max<int32_t>(1, cams_[(size_t)cameraIndex].width);
@@ -326,16 +403,12 @@ public:
         if (want & WantPoint) { h.point.resize(3 * n); g.hits.point = h.point.data(); }
         if (want & WantNormal) { h.normal.resize(3 * n); g.hits.normal = h.normal.data(); }
         if (want & WantFlags) { h.flags.resize(n); g.hits.flags = h.flags.data(); }
-        check(rt_render_gbuffer(scene_, slot, cameraIndex, chunkFirst, chunkStep, &g,
-                                flags & RT_GBUFFER_PIXEL_CENTRE, nullptr));
+        if (mask) check(rt_render_gbuffer_masked(scene_, slot, cameraIndex, chunkFirst, chunkStep, &g,
+                                                 flags & RT_GBUFFER_PIXEL_CENTRE, nullptr, *mask));
+        else check(rt_render_gbuffer(scene_, slot, cameraIndex, chunkFirst, chunkStep, &g,
+                                     flags & RT_GBUFFER_PIXEL_CENTRE, nullptr));
         return f;
     }
-    /* Instance.worldBounds of an instance (any scene), as of the last commit. */
-    void instanceBounds(int32_t instance, double lo[3], double hi[3]) const {
-        check(rt_scene_instance_bounds(scene_, instance, lo, hi));
-    }
-
-private:
     static int32_t fileFormat(SceneFormat f) {
         return f == SceneFormat::Json ? RT_SCENE_FORMAT_JSON : f == SceneFormat::Xml ? RT_SCENE_FORMAT_XML
                                                                                      : RT_SCENE_FORMAT_AUTO;

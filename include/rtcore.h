@@ -423,7 +423,8 @@ int32_t rt_scene_fit_cost(rt_scene* scene, double* cost);
  * one of a scene without objects and every query ray misses.  A hidden instance still takes staged
  * transforms and deformations of its mesh: shown later it has the pose it would have had, and
  * rt_scene_instance_bounds keeps reporting the box it has or would have.  What is NOT possible:
- * instances (or meshes) that did not exist at rt_scene_create_ex, per-ray or per-render masks.
+ * instances (or meshes) that did not exist at rt_scene_create_ex, and masks in renders.  Per-ray masks
+ * for ray queries and first-hit buffers need no commit: "ray masks" at the end of this header.
  *   rt_scene_set_instance_visible   stages a flag (non-zero: visible) until the next commit, like
  *       rt_scene_set_instance_transform: legal while renders are in flight, a second call for the
  *       same instance replaces the first.  RT_ERR_UNSUPPORTED without RT_SCENE_DYNAMIC,
@@ -874,6 +875,58 @@ typedef struct rt_gbuffer {      /* every pointer optional (NULL = not written) 
 int32_t rt_render_gbuffer(rt_scene* scene, int32_t device_slot, int32_t camera_index,
                           int32_t chunk_first, int32_t chunk_step,
                           const rt_gbuffer* out, uint32_t flags, void* stream);
+
+/* ---- ray masks (appended under ABI 5; detect by symbol) ------------------------------
+ * Every instance carries 32 mask bits (0xFFFFFFFF at creation) and a masked query gives every ray 32
+ * mask bits: ray r sees instance k iff (instance_mask[k] & ray_mask[r]) != 0 and k is visible as of
+ * the last commit.  The walk skips an instance the ray does not see where it would enter it, so the
+ * answer is, bit for bit, the unmasked answer for the scene that holds only the instances the ray sees
+ * (a hit on a masked-out instance never hides the hit behind it), and the instance's BLAS is never
+ * entered.  No commit is involved: masks work on static, dynamic and deformable scenes alike, beside
+ * renders in flight.
+ *
+ *   rt_scene_set_instance_masks  masks of instances [first, first + count), applied at once on every
+ *       replica (host side plus one copy per replica).  Masks belong to the scene, not to a commit:
+ *       they survive commits of every kind, instance indices never change, and renders never read
+ *       them.  Ordering the change against queries already enqueued on the caller's streams is the
+ *       caller's job, as for rt_scene_commit.  The per-replica table (4 bytes per instance, counted
+ *       in rt_scene_info.device_bytes) is allocated by the first call, on every replica before any is
+ *       written; until then a masked query treats every instance mask as all-ones.  Refusals, with
+ *       nothing changed: RT_ERR_NO_SCENE; RT_ERR_DEVICE after a failed commit; RT_ERR_INVALID_ARG
+ *       for a range that is not inside the scene's instances or masks == NULL with count > 0;
+ *       RT_ERR_OOM.
+ *   rt_scene_instance_mask       reads one back (0xFFFFFFFF until it was set).
+ *   rt_ray_masks                 the rays' masks of one call: per_ray == NULL gives every ray `all`;
+ *       otherwise one uint32 per ray - a device pointer on the slot's device under RT_QUERY_DEVICE
+ *       (else RT_ERR_UNSUPPORTED), a host array otherwise, staged with the rays in the same passes.
+ *   rt_query_closest_masked / rt_query_occluded_masked   rt_query_closest / rt_query_occluded with
+ *       masks.  masks == NULL is the unmasked call: it ignores instance masks entirely and runs the
+ *       kernels it always ran, as the unmasked entry points do.  A ray with mask 0 misses; it is not
+ *       flagged and counts as a traced ray.  Everything else is the unmasked call's: tMin / tMax and
+ *       time, declared and reduced bounds with their flags, ids / uv / point / normal, query_batch
+ *       launches, rt_query_stats, the walk the scene's options select, equal-t ties re-walked in the
+ *       reference's order (under the same mask), the refusals.
+ *   rt_render_gbuffer_masked     rt_render_gbuffer with ONE mask for the whole call (camera layers,
+ *       picking against selectable objects); the record is rt_query_closest_masked's of the exported
+ *       ray with that mask.
+ * Out of scope: masks in renders (shadow-caster flags, camera layers for rt_render and its
+ * siblings), a tMax for closest-hit queries, ids from occlusion queries. */
+typedef struct rt_ray_masks {
+    const uint32_t* per_ray;        /* NULL: every ray has `all` */
+    uint32_t all;
+    uint32_t pad;
+} rt_ray_masks;
+int32_t rt_scene_set_instance_masks(rt_scene* scene, int32_t first, int32_t count, const uint32_t* masks);
+int32_t rt_scene_instance_mask(const rt_scene* scene, int32_t instance, uint32_t* mask);
+int32_t rt_query_closest_masked(rt_scene* scene, int32_t device_slot, int64_t n, const rt_ray_batch* rays,
+                                const rt_hit_batch* hits, const rt_query_bounds* declared, uint32_t flags,
+                                void* stream, const rt_ray_masks* masks);
+int32_t rt_query_occluded_masked(rt_scene* scene, int32_t device_slot, int64_t n, const rt_ray_batch* rays,
+                                 uint8_t* out, const rt_query_bounds* declared, uint32_t flags, void* stream,
+                                 const rt_ray_masks* masks);
+int32_t rt_render_gbuffer_masked(rt_scene* scene, int32_t device_slot, int32_t camera_index,
+                                 int32_t chunk_first, int32_t chunk_step,
+                                 const rt_gbuffer* out, uint32_t flags, void* stream, uint32_t mask);
 
 #ifdef __cplusplus
 }

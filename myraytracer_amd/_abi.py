@@ -227,6 +227,16 @@ class rt_gbuffer(C.Structure):
 
 GBUFFER_SYMBOLS = ["rt_render_gbuffer"]
 
+# ---- ray masks (rtcore.h "ray masks"; appended under ABI 5: detected by symbol) ----
+
+
+class rt_ray_masks(C.Structure):
+    _fields_ = [("per_ray", C.c_void_p), ("all", C.c_uint32), ("pad", C.c_uint32)]
+
+
+MASK_SYMBOLS = ["rt_scene_set_instance_masks", "rt_scene_instance_mask", "rt_query_closest_masked",
+                "rt_query_occluded_masked", "rt_render_gbuffer_masked"]
+
 RT_MAT = {"": 0, "default": 0, "mirror": 1, "dielectric": 2, "conductor": 3}
 RT_CAM_LOOKAT, RT_CAM_NEARPLANE = 0, 1
 RT_OBJ_MESH, RT_OBJ_TRIANGLE, RT_OBJ_SPHERE, RT_OBJ_PLANE, RT_OBJ_MESH_INSTANCE = 0, 1, 2, 3, 4
@@ -250,6 +260,7 @@ EXPORTED_SYMBOLS = [
     *REBUILD_DETAIL_SYMBOLS,
     *VISIBILITY_SYMBOLS,
     *GBUFFER_SYMBOLS,
+    *MASK_SYMBOLS,
 ]
 RT_ABI_VERSION = 5
 
@@ -397,4 +408,18 @@ def bind(lib: C.CDLL) -> C.CDLL:
         lib.rt_render_gbuffer.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(rt_gbuffer),
                                           C.c_uint32, C.c_void_p]
         lib.rt_render_gbuffer.restype = C.c_int32
+    if hasattr(lib, "rt_scene_set_instance_masks"):   # ray masks (appended under ABI 5: detected by symbol)
+        lib.rt_scene_set_instance_masks.argtypes = [C.c_void_p, C.c_int32, C.c_int32, P(C.c_uint32)]
+        lib.rt_scene_set_instance_masks.restype = C.c_int32
+        lib.rt_scene_instance_mask.argtypes = [C.c_void_p, C.c_int32, P(C.c_uint32)]
+        lib.rt_scene_instance_mask.restype = C.c_int32
+        lib.rt_query_closest_masked.argtypes = [C.c_void_p, C.c_int32, C.c_int64, P(rt_ray_batch), P(rt_hit_batch),
+                                                P(rt_query_bounds), C.c_uint32, C.c_void_p, P(rt_ray_masks)]
+        lib.rt_query_closest_masked.restype = C.c_int32
+        lib.rt_query_occluded_masked.argtypes = [C.c_void_p, C.c_int32, C.c_int64, P(rt_ray_batch), C.c_void_p,
+                                                 P(rt_query_bounds), C.c_uint32, C.c_void_p, P(rt_ray_masks)]
+        lib.rt_query_occluded_masked.restype = C.c_int32
+        lib.rt_render_gbuffer_masked.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, P(rt_gbuffer),
+                                                 C.c_uint32, C.c_void_p, C.c_uint32]
+        lib.rt_render_gbuffer_masked.restype = C.c_int32
     return lib

@@ -271,6 +271,27 @@ constexpr int kMissRef = 0x7fffffff;   // count_ref any-hit: a pushed child whos
 
 struct Hit { double t, u, v; int tri, inst; };
 
+// Ray masks (rtcore.h "ray masks"): the policy every walk asks where it enters an
+// instance, before the instance costs anything.  NoMask is the default of every walk template, so
+// the render kernels and the unmasked queries compile to the code they compiled to without it.
+// RayMask: instance k is seen iff its mask word shares a bit with the ray's (table NULL = no mask
+// was ever set: every instance all-ones); one 4-byte load per instance entered, one VGPR per ray.
+struct NoMask {
+    static constexpr bool kMasked = false;
+    __device__ __forceinline__ constexpr bool pass(int) const { return true; }
+    __device__ __forceinline__ constexpr bool any() const { return true; }
+};
+struct RayMask {
+    static constexpr bool kMasked = true;
+    const uint32_t* table;
+    uint32_t m;
+    __device__ __forceinline__ bool pass(int k) const { return ((table ? table[k] : 0xffffffffu) & m) != 0u; }
+    __device__ __forceinline__ bool any() const { return m != 0u; }       // mask 0: the ray sees nothing
+};
+// pass(k) of the mask in a parameter pack that holds one or none (none: true, and no code)
+template <class... MK>
+__device__ __forceinline__ bool mask_pass(int k, const MK&... mk) { return (mk.pass(k) && ...); }
+
 // Slab test with an explicit hit flag.  FAST = the ray has no zero direction component
 // (every 1/d finite), so no slab value can be NaN: then simd.min/max (minNum/maxNum)
 // and Swift.max/min agree on every comparison the caller makes (they can differ only in
@@ -596,9 +617,15 @@ __device__ __forceinline__ bool walk_any(const RenderParams& P, int ref, const V
     return walk<COUNT, false, SHADOW>(P, ref, o, inv, st, base, c, leaf, limit);
 }
 
-template <bool COUNT>
+// MK: nothing (every caller but the masked queries: the function it always was, out of line), or the
+// ray's RayMask.  A pack, not the `class M = NoMask` of the other walks, and the test under
+// `if constexpr`: here (and in occluded below) even a dead `if (!pass(k))` with a constexpr-true pass
+// changed the spill counts of the eight general-walk kernels that call these two out of line
+// ("Existing kernels are unchanged", what lost (2)); check
+// profiles/masks_resource_usage.txt again after touching either.
+template <bool COUNT, class... MK>
 __device__ void intersect_closest(const RenderParams& P, const V3& o, const V3& d, const V3& inv, double tlo,
-                                  double time, Hit& h, Stack& st, Counts& c) {
+                                  double time, Hit& h, Stack& st, Counts& c, const MK&... mk) {
     const double eps = P.eps;
     h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
     // prune_rel = 1 + delta; reference-order counting walks without pruning
@@ -611,6 +638,8 @@ __device__ void intersect_closest(const RenderParams& P, const V3& o, const V3& 
     auto tlas_leaf = [&](int ref) -> bool {
         for (int e = ~ref - P.tlas_leaf_base;; ++e) {
             const DTlasLeafEntry le = P.tlas_leaf[e];
+            if constexpr (sizeof...(MK) != 0)        // a masked-out instance is not there (discarded without a mask)
+                if (!mask_pass(le.inst, mk...)) { if (le.last) break; continue; }
             const DInstance& I = P.insts[le.inst];
             if (COUNT) c.insts++;
             if (MYRT_REF(P)) c.nodes += 1;   // the BLAS root's bounds (RTContext.swift:550-552)
@@ -656,9 +685,9 @@ __device__ void intersect_closest(const RenderParams& P, const V3& o, const V3& 
     else walk_any<COUNT, false>(P, P.tlas_root_ref, o, inv, st, base, c, tlas_leaf, limit);
 }
 
-template <bool COUNT>
+template <bool COUNT, class... MK>
 __device__ bool occluded(const RenderParams& P, const V3& o, const V3& d, double tmax, double time, Stack& st,
-                         Counts& c) {
+                         Counts& c, const MK&... mk) {
     if (!P.has_tlas) return false;
     const double eps = P.eps;
     const V3 inv = rcp(d);
@@ -672,6 +701,8 @@ __device__ bool occluded(const RenderParams& P, const V3& o, const V3& d, double
     auto tlas_leaf = [&](int ref) -> bool {
         for (int e = ~ref - P.tlas_leaf_base;; ++e) {
             const DTlasLeafEntry le = P.tlas_leaf[e];
+            if constexpr (sizeof...(MK) != 0)
+                if (!mask_pass(le.inst, mk...)) { if (le.last) break; continue; }
             const DInstance& I = P.insts[le.inst];
             if (COUNT) c.insts++;
             if (MYRT_REF(P)) c.nodes += 1;   // occludedBLAS pops its root (RTContext.swift:789-793)
@@ -724,9 +755,10 @@ __device__ bool occluded(const RenderParams& P, const V3& o, const V3& d, double
 // 2 = shadow ray occluded.
 // Leaf of the unified walk: a BLAS leaf run (closest: record hits in h; any-hit: true when
 // occluded) or a TLAS leaf (pushes its instances' BLAS roots in reverse order).
-template <bool COUNT, bool SHADOW, bool FAST>
+template <bool COUNT, bool SHADOW, bool FAST, class M = NoMask>
 __device__ __forceinline__ bool unified_leaf(const RenderParams& P, int ref, Stack& st, const V3& o, const V3& d,
-                                             const V3& inv, double tlo, double tmax, Hit& h, Counts& c) {
+                                             const V3& inv, double tlo, double tmax, Hit& h, Counts& c,
+                                             const M& mk = M{}) {
     const double eps = P.eps;
     const int e = ~ref;
     if (e < P.tlas_leaf_base) {                                  // BLAS leaf run
@@ -752,6 +784,7 @@ __device__ __forceinline__ bool unified_leaf(const RenderParams& P, int ref, Sta
     while (!P.tlas_leaf[k1].last) ++k1;
     const double lim = (SHADOW ? tmax : h.t) * P.prune_rel + P.prune_abs;
     for (int k = k1; k >= k0; --k) {
+        if (!mk.pass(P.tlas_leaf[k].inst)) continue;
         const DInstance& I = P.insts[P.tlas_leaf[k].inst];
         if (COUNT) c.insts++;
         double dr;
@@ -762,9 +795,10 @@ __device__ __forceinline__ bool unified_leaf(const RenderParams& P, int ref, Sta
     return false;
 }
 
-template <bool COUNT, bool SHADOW, bool FAST>
+template <bool COUNT, bool SHADOW, bool FAST, class M = NoMask>
 __device__ __forceinline__ int unified_step(const RenderParams& P, int& ref, Stack& st, const V3& o, const V3& d,
-                                            const V3& inv, double tlo, double tmax, Hit& h, Counts& c) {
+                                            const V3& inv, double tlo, double tmax, Hit& h, Counts& c,
+                                            const M& mk = M{}) {
     if (COUNT && !P.count_ref) {             // divergence breakdown of this iteration
         const bool in = ref >= 0;
         const unsigned long long bi = __ballot(in), bl = __ballot(!in);
@@ -777,7 +811,7 @@ __device__ __forceinline__ int unified_step(const RenderParams& P, int& ref, Sta
     if (ref >= 0) {
         if (inner_step<COUNT, FAST, SHADOW>(P, ref, o, inv, (SHADOW ? tmax : h.t) * P.prune_rel + P.prune_abs, st, c))
             return 0;
-    } else if (unified_leaf<COUNT, SHADOW, FAST>(P, ref, st, o, d, inv, tlo, tmax, h, c)) {
+    } else if (unified_leaf<COUNT, SHADOW, FAST>(P, ref, st, o, d, inv, tlo, tmax, h, c, mk)) {
         return 2;
     }
     return pop_next<COUNT, SHADOW>(P, st, 0, (SHADOW ? tmax : h.t) * P.prune_rel + P.prune_abs, ref, c) ? 0 : 1;
@@ -804,38 +838,38 @@ namespace dev {
 // wide tree (RenderParams::wide) and every 1/d in range, the conservative FP32 four-wide walk
 // (wide.h) runs instead; a lane that met two candidates at its final t is re-walked here in
 // the reference's order.  Reference-order counting launches (count_ref) keep the binary walk.
-template <bool COUNT, bool FAST>
+template <bool COUNT, bool FAST, class M = NoMask>
 __device__ __forceinline__ void uni_closest_walk(const RenderParams& P, const V3& o, const V3& d, const V3& inv,
-                                                 double tlo, Hit& h, Stack& st, Counts& c) {
+                                                 double tlo, Hit& h, Stack& st, Counts& c, const M& mk = M{}) {
     int ref;
     if (!unified_begin(P, o, inv, DINF, ref)) return;   // the stack is empty here (base 0)
     do {
         if (COUNT || MYRT_WAVE_TIMES) c.it_closest++;
-    } while (unified_step<COUNT, false, FAST>(P, ref, st, o, d, inv, tlo, DINF, h, c) == 0);
+    } while (unified_step<COUNT, false, FAST>(P, ref, st, o, d, inv, tlo, DINF, h, c, mk) == 0);
 }
-template <bool COUNT, bool WIDE = true>
+template <bool COUNT, bool WIDE = true, class M = NoMask>
 __device__ __forceinline__ void uni_closest(const RenderParams& P, const V3& o, const V3& d, const V3& inv,
-                                            double tlo, Hit& h, Stack& st, Counts& c) {
+                                            double tlo, Hit& h, Stack& st, Counts& c, const M& mk = M{}) {
     h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
     if (WIDE && !MYRT_REF(P) && P.wide && __all(wide_ok(inv))) {
         bool tie = false;
-        (void)wide_walk<COUNT, false>(P, TwWorld{o, d}, inv, tlo, DINF, h, tie, st, c);
+        (void)wide_walk<COUNT, false>(P, TwWorld{o, d}, inv, tlo, DINF, h, tie, st, c, mk);
 #ifndef MYRT_REWALK
 #define MYRT_REWALK 1
 #endif
         if (MYRT_REWALK && __any(tie) && tie) {  // equal-t candidates: the reference's order decides
             c.ties++;
             h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
-            uni_closest_walk<COUNT, true>(P, o, d, inv, tlo, h, st, c);
+            uni_closest_walk<COUNT, true>(P, o, d, inv, tlo, h, st, c, mk);
         }
         return;
     }
-    if (__all(finite3(inv))) uni_closest_walk<COUNT, true>(P, o, d, inv, tlo, h, st, c);
-    else uni_closest_walk<COUNT, false>(P, o, d, inv, tlo, h, st, c);
+    if (__all(finite3(inv))) uni_closest_walk<COUNT, true>(P, o, d, inv, tlo, h, st, c, mk);
+    else uni_closest_walk<COUNT, false>(P, o, d, inv, tlo, h, st, c, mk);
 }
-template <bool COUNT, bool FAST>
+template <bool COUNT, bool FAST, class M = NoMask>
 __device__ __forceinline__ bool uni_occluded_walk(const RenderParams& P, const V3& o, const V3& d, const V3& inv,
-                                                  double tmax, Stack& st, Counts& c) {
+                                                  double tmax, Stack& st, Counts& c, const M& mk = M{}) {
     int ref;
     if (!unified_begin(P, o, inv, tmax * P.prune_rel + P.prune_abs, ref)) return false;
     Hit h;   // unused by any-hit steps
@@ -844,22 +878,22 @@ __device__ __forceinline__ bool uni_occluded_walk(const RenderParams& P, const V
     int r;
     do {
         if (COUNT || MYRT_WAVE_TIMES) c.it_shadow++;
-    } while ((r = unified_step<COUNT, true, FAST>(P, ref, st, o, d, inv, 0.0, tmax, h, c)) == 0);
+    } while ((r = unified_step<COUNT, true, FAST>(P, ref, st, o, d, inv, 0.0, tmax, h, c, mk)) == 0);
     st.reset(base);
     return r == 2;
 }
-template <bool COUNT, bool WIDE = true>
+template <bool COUNT, bool WIDE = true, class M = NoMask>
 __device__ __forceinline__ bool uni_occluded(const RenderParams& P, const V3& o, const V3& d, double tmax,
-                                             Stack& st, Counts& c) {
+                                             Stack& st, Counts& c, const M& mk = M{}) {
     if (!P.has_tlas) return false;
     const V3 inv = rcp(d);
     if (WIDE && !MYRT_REF(P) && P.wide && __all(wide_ok(inv))) {
         Hit hu;
         bool tie = false;
-        return wide_walk<COUNT, true>(P, TwWorld{o, d}, inv, 0.0, tmax, hu, tie, st, c);
+        return wide_walk<COUNT, true>(P, TwWorld{o, d}, inv, 0.0, tmax, hu, tie, st, c, mk);
     }
-    if (__all(finite3(inv))) return uni_occluded_walk<COUNT, true>(P, o, d, inv, tmax, st, c);
-    return uni_occluded_walk<COUNT, false>(P, o, d, inv, tmax, st, c);
+    if (__all(finite3(inv))) return uni_occluded_walk<COUNT, true>(P, o, d, inv, tmax, st, c, mk);
+    return uni_occluded_walk<COUNT, false>(P, o, d, inv, tmax, st, c, mk);
 }
 
 // Walks of the render kernels (render.hip WALK template argument)
@@ -907,14 +941,15 @@ __device__ __forceinline__ bool ut_is_tlas(const RenderParams& P, int ref) {
 // (a sphere/plane instance's primitive is tested right there, `prim`); TLAS entries bring the
 // world ray back.  Returns 0 = `ref` holds the next node, 1 = stack exhausted, 2 = occluded
 // (SHADOW: a sphere/plane instance's primitive blocks the ray).
-template <bool SHADOW, class Prim>
+template <bool SHADOW, class Prim, class M>
 __device__ __forceinline__ int ut_pop(const RenderParams& P, Stack& st, int base, double lim, int& ref, UtRay& R,
-                                      const V3& o, const V3& d, double time, Prim prim) {
+                                      const V3& o, const V3& d, double time, Prim prim, const M& mk) {
     while (st.sp > base) {
         double tlo;
         const int r = st.pop(tlo);
         if (ut_is_marker(P, r)) {
             const int k = ~r - P.ut_marker_base;
+            if (!mk.pass(k)) continue;                 // masked out: the ray is left as it is, as on a root miss
             ut_local(P, R, k, o, d, time);
             const DInstance& I = P.insts[k];
             double dr;
@@ -938,9 +973,9 @@ __device__ __forceinline__ int ut_pop(const RenderParams& P, Stack& st, int base
 
 // Closest hit (intersectTLAS) or any hit (occludedTLAS, order-free) of one world ray.
 // Returns the occlusion for SHADOW.
-template <bool SHADOW>
+template <bool SHADOW, class M = NoMask>
 __device__ __forceinline__ bool ut_walk(const RenderParams& P, const V3& o, const V3& d, const V3& inv, double tlo,
-                                        double tmax, double time, Hit& h, Stack& st) {
+                                        double tmax, double time, Hit& h, Stack& st, const M& mk = M{}) {
     Counts c{};
     const double eps = P.eps;
     const int base = st.sp;
@@ -986,7 +1021,7 @@ __device__ __forceinline__ bool ut_walk(const RenderParams& P, const V3& o, cons
         }
         if (stepped) continue;
         const double lim2 = (SHADOW ? tmax : h.t) * P.prune_rel + P.prune_abs;
-        const int pr = ut_pop<SHADOW>(P, st, base, lim2, ref, R, o, d, time, prim);
+        const int pr = ut_pop<SHADOW>(P, st, base, lim2, ref, R, o, d, time, prim, mk);
         if (pr == 2) { occ = true; break; }
         if (pr == 1) break;
     }

@@ -133,6 +133,33 @@ __global__ __launch_bounds__(64) void k_gbuffer(RenderParams P, QueryBatch B, GB
     query_count(B, hit, cls);
 }
 
+// rt_render_gbuffer_masked: the kernel above with one ray mask for the whole call (QueryMasks::all),
+// a kernel of its own as the masked queries are (query.h), so that k_gbuffer stays the code it was.
+template <int WALK>
+__global__ __launch_bounds__(64) void k_gbuffer_masked(RenderParams P, QueryBatch B, GBufferBatch G, QueryMasks K) {
+    extern __shared__ unsigned long long lds_stack[];
+    MYRT_STACK(st, lds_stack);
+    Counts c{};
+    bool hit = false;
+    uint32_t cls = 0u;
+    int i, j;
+    size_t at;
+    if (gbuffer_pixel(P, G, i, j, at)) {
+        V3 o, d;
+        double tlo, time;
+        first_ray(P, i, j, G.centre != 0u, o, d, tlo, time);
+        gbuffer_store_ray(G, at, o, d, tlo, time);
+        cls = query_finite(o, d) ? 0u : (uint32_t)RT_HIT_NON_FINITE;
+        const RayMask mk{K.table, K.all};
+        Hit h;
+        h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
+        if (cls == 0u && P.has_tlas && mk.any()) walk_closest<false, WALK>(P, o, d, rcp(d), tlo, time, h, st, c, mk);
+        hit = h.inst >= 0;
+        query_record(P, B, at, o, d, time, h, hit, cls, c);
+    }
+    query_count(B, hit, cls);
+}
+
 // Rays only (no record pointer set): no stack, no LDS, none of a walk's registers.
 constexpr int kGBufferRaysBlock = 256;
 __global__ __launch_bounds__(kGBufferRaysBlock) void k_gbuffer_rays(RenderParams P, GBufferBatch G) {

@@ -33,6 +33,16 @@ struct QueryBatch {
     uint32_t mask;
 };
 
+// The masks of a launch (rt_query_*_masked, rt_render_gbuffer_masked), a kernel
+// argument of its own next to QueryBatch::mask: the scene's instance-mask table (NULL until masks
+// are first set: every instance all-ones) and the rays' masks, one per ray of this launch or `all`.
+// at(i) is ray i's policy for the walks (device.h RayMask).
+struct QueryMasks {
+    const uint32_t *table, *per_ray;
+    uint32_t all, pad;
+    __device__ __forceinline__ RayMask at(size_t i) const { return RayMask{table, per_ray ? per_ray[i] : all}; }
+};
+
 // 0: trace the ray; RT_HIT_NON_FINITE / RT_HIT_OUT_OF_BOUNDS: report it untraced.  The three
 // magnitudes are formed term for term as the host forms a camera's (render.hip dist_to_center,
 // make_params).
@@ -139,6 +149,58 @@ __global__ __launch_bounds__(64) void k_query_occluded(RenderParams P, QueryBatc
             if (WALK == kWalkIdentity) hit = uni_occluded<false>(P, o, d, tmax, st, c);
             else if (WALK == kWalkGeneral) hit = occluded<false>(P, o, d, tmax, time, st, c);
             else hit = walk_occluded<false, WALK, true, false>(P, o, d, tmax, time, st, c);
+        }
+        B.occ[i] = cls ? (uint8_t)2 : (hit ? (uint8_t)1 : (uint8_t)0);
+    }
+    query_count(B, hit, cls);
+}
+
+// The masked queries (rt_query_closest_masked / rt_query_occluded_masked): the two kernels above with
+// ray i's mask handed to the walk.  They are kernels of their own, not a parameter of the ones above,
+// so the unmasked kernels stay the code they were: same attributes, same helpers, and a ray whose
+// mask is 0 sees nothing and is not walked (a miss, not flagged, counted as traced).
+template <int WALK>
+__global__ __launch_bounds__(64) void k_query_closest_masked(RenderParams P, QueryBatch B, QueryMasks K) {
+    extern __shared__ unsigned long long lds_stack[];
+    const int i = (int)(blockIdx.x * 64u + threadIdx.x);
+    MYRT_STACK(st, lds_stack);
+    Counts c{};
+    bool hit = false;
+    uint32_t cls = 0u;
+    if (i < B.n) {
+        const size_t i3 = 3 * (size_t)i;
+        const V3 o = v3(B.o[i3], B.o[i3 + 1], B.o[i3 + 2]), d = v3(B.d[i3], B.d[i3 + 1], B.d[i3 + 2]);
+        const double time = (B.mask & kQHasTime) ? B.time[i] : 0.0;
+        cls = query_class(B, o, d);
+        const RayMask mk = K.at((size_t)i);
+        Hit h;
+        h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
+        if (cls == 0u && P.has_tlas && mk.any()) {
+            const double tlo = (B.mask & kQHasTlim) ? B.tlim[i] : 0.0;
+            walk_closest<false, WALK>(P, o, d, rcp(d), tlo, time, h, st, c, mk);
+        }
+        hit = h.inst >= 0;
+        query_record(P, B, (size_t)i, o, d, time, h, hit, cls, c);
+    }
+    query_count(B, hit, cls);
+}
+template <int WALK>
+__global__ __launch_bounds__(64) void k_query_occluded_masked(RenderParams P, QueryBatch B, QueryMasks K) {
+    extern __shared__ unsigned long long lds_stack[];
+    const int i = (int)(blockIdx.x * 64u + threadIdx.x);
+    MYRT_STACK(st, lds_stack);
+    Counts c{};
+    bool hit = false;
+    uint32_t cls = 0u;
+    if (i < B.n) {
+        const size_t i3 = 3 * (size_t)i;
+        const V3 o = v3(B.o[i3], B.o[i3 + 1], B.o[i3 + 2]), d = v3(B.d[i3], B.d[i3 + 1], B.d[i3 + 2]);
+        cls = query_class(B, o, d);
+        const RayMask mk = K.at((size_t)i);
+        if (cls == 0u && mk.any()) {
+            const double tmax = (B.mask & kQHasTlim) ? B.tlim[i] : DINF;
+            const double time = (B.mask & kQHasTime) ? B.time[i] : 0.0;
+            hit = walk_occluded<false, WALK, true, false>(P, o, d, tmax, time, st, c, mk);
         }
         B.occ[i] = cls ? (uint8_t)2 : (hit ? (uint8_t)1 : (uint8_t)0);
     }

@@ -52,66 +52,75 @@ __device__ __forceinline__ unsigned long long pixel_seed(int i, int j) {
 #else
 #define MYRT_TW_INLINE __forceinline__
 #endif
+// (M: the ray's mask, device.h; the re-walks carry it, or a tie would bring a masked-out instance back)
+template <class M = NoMask>
 __device__ MYRT_TW_INLINE void ut_closest_call(const RenderParams& P, const V3 o, const V3 d, const V3 inv, double tlo,
-                                            double time, Hit& h, Stack& st) {
+                                            double time, Hit& h, Stack& st, const M& mk = M{}) {
     h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
-    (void)ut_walk<false>(P, o, d, inv, tlo, DINF, time, h, st);
+    (void)ut_walk<false>(P, o, d, inv, tlo, DINF, time, h, st, mk);
 }
+template <class M = NoMask>
 __device__ MYRT_TW_INLINE bool ut_occluded_call(const RenderParams& P, const V3 o, const V3 d, double tmax, double time,
-                                             Stack& st) {
+                                             Stack& st, const M& mk = M{}) {
     Hit hu;
-    return ut_walk<true>(P, o, d, rcp(d), 0.0, tmax, time, hu, st);
+    return ut_walk<true>(P, o, d, rcp(d), 0.0, tmax, time, hu, st, mk);
 }
 
 // The flattened instance tree's fallbacks (equal-t ties, world rays out of the FP32 range): the
 // reference-order transformed walk.  (Out of line, __noinline__, the megakernel went to 212 VGPRs
 // and 144 spills: a call costs the kernel its register budget.)
+template <class M = NoMask>
 __device__ __forceinline__ void fit_closest_fallback(const RenderParams& P, const V3 o, const V3 d, double tlo, double time,
-                                                  Hit& h, Stack& st) {
+                                                  Hit& h, Stack& st, const M& mk = M{}) {
     h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
-    (void)ut_walk<false>(P, o, d, rcp(d), tlo, DINF, time, h, st);
+    (void)ut_walk<false>(P, o, d, rcp(d), tlo, DINF, time, h, st, mk);
 }
+template <class M = NoMask>
 __device__ __forceinline__ bool fit_occluded_fallback(const RenderParams& P, const V3 o, const V3 d, double tmax,
-                                                   double time, Stack& st) {
+                                                   double time, Stack& st, const M& mk = M{}) {
     Hit hu;
-    return ut_walk<true>(P, o, d, rcp(d), 0.0, tmax, time, hu, st);
+    return ut_walk<true>(P, o, d, rcp(d), 0.0, tmax, time, hu, st, mk);
 }
 
 // Closest hit of one ray by the scene's walk (WALK, render_kernel).
-template <bool COUNT, int WALK, bool WIDE = true>
+// M: the ray's mask (device.h NoMask / RayMask), handed to the walk and to its re-walks; the
+// general walk's masked form is called by the masked kernels themselves (query.h).
+template <bool COUNT, int WALK, bool WIDE = true, class M = NoMask>
 __device__ __forceinline__ void walk_closest(const RenderParams& P, const V3& o, const V3& d, const V3& inv, double tlo,
-                                             double time, Hit& h, Stack& st, Counts& c) {
+                                             double time, Hit& h, Stack& st, Counts& c, const M& mk = M{}) {
     if (WALK == kWalkIdentity) {
-        uni_closest<COUNT, WIDE>(P, o, d, inv, tlo, h, st, c);
+        uni_closest<COUNT, WIDE>(P, o, d, inv, tlo, h, st, c, mk);
     } else if (WALK == kWalkFit) {
         h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
         if (WIDE && __all(wide_ok(inv))) {
             // the flattened instance tree (wide.h fit_walk); equal-t candidates re-walked in order
             bool tie = false;
-            (void)wide_walk<COUNT, false, true>(P, TwWorld{o, d}, inv, tlo, DINF, h, tie, st, c);
+            (void)wide_walk<COUNT, false, true>(P, TwWorld{o, d}, inv, tlo, DINF, h, tie, st, c, mk);
             if (__any(tie) && tie) {
                 c.ties++;
-                fit_closest_fallback(P, o, d, tlo, time, h, st);
+                fit_closest_fallback(P, o, d, tlo, time, h, st, mk);
             }
             return;
         }
-        fit_closest_fallback(P, o, d, tlo, time, h, st);
+        fit_closest_fallback(P, o, d, tlo, time, h, st, mk);
     } else if (WALK == kWalkTransformed) {
         h.t = DINF; h.inst = -1; h.tri = -1; h.u = 0; h.v = 0;
         if (WIDE && P.wide && P.winst && __all(wide_ok(inv))) {
             // the four-wide walk of transformed scenes (wide.h tw_walk); equal-t candidates and
             // local rays out of its range are re-walked in the reference's order
             bool tie = false, redo = false;
-            (void)tw_walk<false>(P, TwWorld{o, d}, tlo, DINF, h, tie, redo, st);
+            (void)tw_walk<false>(P, TwWorld{o, d}, tlo, DINF, h, tie, redo, st, mk);
             if (__any(tie || redo) && (tie || redo)) {
                 if (tie) c.ties++;
-                ut_closest_call(P, o, d, inv, tlo, time, h, st);
+                ut_closest_call(P, o, d, inv, tlo, time, h, st, mk);
             }
             return;
         }
-        (void)ut_walk<false>(P, o, d, inv, tlo, DINF, time, h, st);
-    } else {
+        (void)ut_walk<false>(P, o, d, inv, tlo, DINF, time, h, st, mk);
+    } else if constexpr (!M::kMasked) {
         intersect_closest<COUNT>(P, o, d, inv, tlo, time, h, st, c);
+    } else {
+        intersect_closest<COUNT>(P, o, d, inv, tlo, time, h, st, c, mk);
     }
 }
 
@@ -159,10 +168,11 @@ __device__ __forceinline__ void walk_closest_fit_parked(const RenderParams& P, c
 }
 
 // Any hit of one shadow ray (tMin 0, tMax) by the scene's walk.
-template <bool COUNT, int WALK, bool WIDE = true, bool PARK = (MYRT_TW_PARK != 0), class WPark = TwParked>
+template <bool COUNT, int WALK, bool WIDE = true, bool PARK = (MYRT_TW_PARK != 0), class WPark = TwParked,
+          class M = NoMask>
 __device__ __forceinline__ bool walk_occluded(const RenderParams& P, const V3& o, const V3& d, double tmax, double time,
-                                              Stack& st, Counts& c) {
-    if (WALK == kWalkIdentity) return uni_occluded<COUNT, WIDE>(P, o, d, tmax, st, c);
+                                              Stack& st, Counts& c, const M& mk = M{}) {
+    if (WALK == kWalkIdentity) return uni_occluded<COUNT, WIDE>(P, o, d, tmax, st, c, mk);
     if (WALK == kWalkFit) {
         if (!P.has_tlas) return false;
         Hit hu;
@@ -172,11 +182,11 @@ __device__ __forceinline__ bool walk_occluded(const RenderParams& P, const V3& o
             if (PARK && MYRT_FIT_PARK) {
                 WPark pk;                                 // private memory, or the megakernel's LDS slots
                 pk.store(o, d);
-                return wide_walk<COUNT, true, true>(P, pk, inv, 0.0, tmax, hu, tie, st, c);
+                return wide_walk<COUNT, true, true>(P, pk, inv, 0.0, tmax, hu, tie, st, c, mk);
             }
-            return wide_walk<COUNT, true, true>(P, TwWorld{o, d}, inv, 0.0, tmax, hu, tie, st, c);
+            return wide_walk<COUNT, true, true>(P, TwWorld{o, d}, inv, 0.0, tmax, hu, tie, st, c, mk);
         }
-        return fit_occluded_fallback(P, o, d, tmax, time, st);
+        return fit_occluded_fallback(P, o, d, tmax, time, st, mk);
     }
     if (WALK == kWalkTransformed) {
         if (!P.has_tlas) return false;
@@ -188,16 +198,17 @@ __device__ __forceinline__ bool walk_occluded(const RenderParams& P, const V3& o
             if (PARK) {
                 WPark pk;                                 // private memory, or the megakernel's LDS slots
                 pk.store(o, d);
-                occ = tw_walk<true>(P, pk, 0.0, tmax, hu, tie, redo, st);
+                occ = tw_walk<true>(P, pk, 0.0, tmax, hu, tie, redo, st, mk);
             } else {
-                occ = tw_walk<true>(P, TwWorld{o, d}, 0.0, tmax, hu, tie, redo, st);
+                occ = tw_walk<true>(P, TwWorld{o, d}, 0.0, tmax, hu, tie, redo, st, mk);
             }
             if (!redo) return occ;
-            return ut_occluded_call(P, o, d, tmax, time, st);
+            return ut_occluded_call(P, o, d, tmax, time, st, mk);
         }
-        return ut_walk<true>(P, o, d, inv, 0.0, tmax, time, hu, st);
+        return ut_walk<true>(P, o, d, inv, 0.0, tmax, time, hu, st, mk);
     }
-    return occluded<COUNT>(P, o, d, tmax, time, st, c);
+    if constexpr (!M::kMasked) return occluded<COUNT>(P, o, d, tmax, time, st, c);
+    else return occluded<COUNT>(P, o, d, tmax, time, st, c, mk);
 }
 
 // Point lights at a hit (Object+Extension.swift:116-143): adds the unoccluded Blinn-Phong
@@ -1357,6 +1368,8 @@ struct DeviceReplica {
     int32_t* q_face = nullptr;
     int32_t* q_inst_obj = nullptr;
     rt_query_counts q_last{};
+    // ray masks (rtcore.h "ray masks"): one word per instance, NULL until masks are first set
+    uint32_t* inst_masks = nullptr;
 };
 
 }  // namespace
@@ -1455,6 +1468,7 @@ struct rt_scene {
     rt_deform_stats last_deform{};
     rt_rebuild_stats last_rebuild{};                  // of the last successful commit (rt_scene_commit_ex)
     rt_rebuild_detail last_detail{};                  // ... and which builder made the tree (rt_scene_last_rebuild_detail)
+    std::vector<uint32_t> inst_masks;                 // rt_scene_set_instance_masks: empty until the first call (all-ones)
     AllocGate gate;                                   // the device allocations of a commit (armed by commit_impl only)
     // A commit that failed on the device after it began to write left the scene in no pose at all:
     // from then on every call that reads or writes the scene returns RT_ERR_DEVICE (scene_lost);
@@ -1558,6 +1572,7 @@ static void free_replica(DeviceReplica& r) {
     (void)hipFree(r.vid); (void)hipFree(r.rec_list); (void)hipFree(r.wide_list); (void)hipFree(r.csr_off); (void)hipFree(r.csr_tri);
     r.def_stage.release(); r.def_face.release(); r.def_vnorm.release(); r.def_part.release(); r.def_out.release();
     (void)hipFree(r.q_buf); (void)hipFree(r.q_words); (void)hipFree(r.q_face); (void)hipFree(r.q_inst_obj);
+    (void)hipFree(r.inst_masks);
     if (r.q_host) (void)hipHostFree(r.q_host);
     r.full.release();
     r.dev_full.release();
@@ -3500,12 +3515,18 @@ int32_t rt_debug_wide_read(rt_scene* s, int32_t slot, rt_wide_dump* io) {
 // ---- ray queries (rtcore.h "ray queries"; query.h) ------------------------------------
 // A host-array query is staged through r.q_buf in passes of at most `m` rays: per ray 17 doubles
 // (o, d, tlimit, time in; t, uv, point, normal out), the four ids and the two byte arrays.
+// A host array of per-ray masks (rt_query_*_masked) takes one more word per ray, behind the rest.
 constexpr int64_t kQueryStageBytes = 17 * 8 + 4 * 4 + 2;
+constexpr int64_t kQueryStageMaskBytes = 4;
 struct QueryStage {
     double *o, *d, *tlim, *time, *t, *uv, *point, *normal;
     int32_t* ids;
     uint8_t *flags, *occ;
+    uint32_t* masks;
 };
+static int64_t query_stage_bytes(int64_t m, bool masks) {
+    return masks ? (m * kQueryStageBytes + 3) / 4 * 4 + m * kQueryStageMaskBytes : m * kQueryStageBytes;
+}
 static QueryStage query_stage(uint8_t* base, int64_t m) {
     QueryStage q;
     double* p = (double*)base;
@@ -3514,6 +3535,7 @@ static QueryStage query_stage(uint8_t* base, int64_t m) {
     q.ids = (int32_t*)p;
     q.flags = (uint8_t*)(q.ids + 4 * m);
     q.occ = q.flags + m;
+    q.masks = (uint32_t*)(base + query_stage_bytes(m, true) - m * kQueryStageMaskBytes);
     return q;
 }
 static bool on_device(const void* p, int device) {
@@ -3524,7 +3546,7 @@ static bool on_device(const void* p, int device) {
 
 // The slot's query scratch, under the scene's lock: the query words and their pinned copy, the face
 // table on the first call that asks for ids, and staging for `stage` rays of a host-array call.
-static int32_t query_scratch(const HostScene& S, DeviceReplica& r, bool ids, int64_t stage) {
+static int32_t query_scratch(const HostScene& S, DeviceReplica& r, bool ids, int64_t stage, bool stage_masks = false) {
     if (!r.q_words) HIP_TRY(hipMalloc((void**)&r.q_words, dev::kQWords * 8));
     if (!r.q_host) HIP_TRY(hipHostMalloc((void**)&r.q_host, dev::kQWords * 8, hipHostMallocDefault));
     if (ids && !r.q_face) {
@@ -3538,13 +3560,15 @@ static int32_t query_scratch(const HostScene& S, DeviceReplica& r, bool ids, int
         }
         r.bytes += (int64_t)(S.face.size() + S.inst_obj.size()) * 4;
     }
-    if (stage > 0 && !grow_buf(r, &r.q_buf, r.q_cap, stage * kQueryStageBytes, 1))
+    if (stage > 0 && !grow_buf(r, &r.q_buf, r.q_cap, query_stage_bytes(stage, stage_masks), 1))
         return fail(RT_ERR_OOM, "query staging does not fit on the device");
     return RT_OK;
 }
 
+// masks != NULL: a masked query (the *_masked kernels); NULL: the unmasked call, on the kernels it always used
 static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, const rt_hit_batch* hits,
-                          uint8_t* occ, bool occluded, const rt_query_bounds* declared, uint32_t flags, void* stream_) {
+                          uint8_t* occ, bool occluded, const rt_query_bounds* declared, uint32_t flags, void* stream_,
+                          const rt_ray_masks* masks = nullptr) {
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
     if (const int32_t rc = scene_lost(s)) return rc;
     if (slot < 0 || slot >= (int32_t)s->devs.size()) return fail(RT_ERR_INVALID_ARG, "bad device slot");
@@ -3561,7 +3585,8 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
     if (on_dev && n > 0) {
         for (const void* p : {(const void*)rays->origin, (const void*)rays->dir, (const void*)rays->tlimit,
                               (const void*)rays->time, (const void*)H.t, (const void*)H.uv, (const void*)H.ids,
-                              (const void*)H.point, (const void*)H.normal, (const void*)H.flags, (const void*)occ})
+                              (const void*)H.point, (const void*)H.normal, (const void*)H.flags, (const void*)occ,
+                              (const void*)(masks ? masks->per_ray : nullptr)})
             if (p && !on_device(p, r.device))
                 return fail(RT_ERR_UNSUPPORTED, "RT_QUERY_DEVICE: not a device pointer on the slot's device");
     }
@@ -3570,6 +3595,8 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
     RenderParams P;
     int64_t batch = 0;
     double center[3];
+    const uint32_t* ray_masks = masks ? masks->per_ray : nullptr;
+    dev::QueryMasks K{};
     {   // prepared under the scene's lock: parameters, options, the slot's query scratch
         std::lock_guard<std::mutex> lock(s->mu);
         HIP_TRY(hipSetDevice(r.device));
@@ -3578,7 +3605,11 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
         P = make_params(s, r, 0, 0, 1, nullptr, nullptr);
         batch = s->opt[kOptQueryBatch];
         for (int k = 0; k < 3; ++k) center[k] = S.scene_center[k];
-        if (const int32_t rc = query_scratch(S, r, H.ids != nullptr, on_dev ? 0 : std::min(n, batch))) return rc;
+        if (const int32_t rc = query_scratch(S, r, H.ids != nullptr, on_dev ? 0 : std::min(n, batch),
+                                             !on_dev && ray_masks != nullptr))
+            return rc;
+        K.table = r.inst_masks;
+        K.all = masks ? masks->all : 0xffffffffu;
     }
     const int64_t m_max = std::min(n, batch);
     const int64_t launches = (n + batch - 1) / batch;
@@ -3636,6 +3667,7 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
             B.point = H.point ? H.point + 3 * base : nullptr; B.normal = H.normal ? H.normal + 3 * base : nullptr;
             B.flags = H.flags ? H.flags + base : nullptr;
             B.occ = occ ? occ + base : nullptr;
+            K.per_ray = ray_masks ? ray_masks + base : nullptr;
         } else {
             if (!staged_od) {
                 HIP_TRY(hipMemcpyAsync(st.o, rays->origin + 3 * base, (size_t)m * 24, hipMemcpyHostToDevice, stream));
@@ -3643,6 +3675,8 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
             }
             if (rays->tlimit) HIP_TRY(hipMemcpyAsync(st.tlim, rays->tlimit + base, (size_t)m * 8, hipMemcpyHostToDevice, stream));
             if (rays->time) HIP_TRY(hipMemcpyAsync(st.time, rays->time + base, (size_t)m * 8, hipMemcpyHostToDevice, stream));
+            if (ray_masks) HIP_TRY(hipMemcpyAsync(st.masks, ray_masks + base, (size_t)m * 4, hipMemcpyHostToDevice, stream));
+            K.per_ray = ray_masks ? st.masks : nullptr;
             B.o = st.o; B.d = st.d; B.tlim = rays->tlimit ? st.tlim : nullptr; B.time = rays->time ? st.time : nullptr;
             B.t = H.t ? st.t : nullptr; B.uv = H.uv ? st.uv : nullptr; B.ids = H.ids ? st.ids : nullptr;
             B.point = H.point ? st.point : nullptr; B.normal = H.normal ? st.normal : nullptr;
@@ -3652,8 +3686,15 @@ static int32_t query_impl(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
         const size_t lds = (size_t)dev::kLds * kRenderBlock * sizeof(unsigned long long);
 #define MYRT_QOCC(W_) hipLaunchKernelGGL((dev::k_query_occluded<W_>), grid, block, lds, stream, P, B)
 #define MYRT_QHIT(W_) hipLaunchKernelGGL((dev::k_query_closest<W_>), grid, block, lds, stream, P, B)
-        if (occluded) MYRT_BY_WALK(MYRT_QOCC);
+#define MYRT_QOCCM(W_) hipLaunchKernelGGL((dev::k_query_occluded_masked<W_>), grid, block, lds, stream, P, B, K)
+#define MYRT_QHITM(W_) hipLaunchKernelGGL((dev::k_query_closest_masked<W_>), grid, block, lds, stream, P, B, K)
+        if (masks) {
+            if (occluded) MYRT_BY_WALK(MYRT_QOCCM);
+            else MYRT_BY_WALK(MYRT_QHITM);
+        } else if (occluded) MYRT_BY_WALK(MYRT_QOCC);
         else MYRT_BY_WALK(MYRT_QHIT);
+#undef MYRT_QHITM
+#undef MYRT_QOCCM
 #undef MYRT_QHIT
 #undef MYRT_QOCC
         HIP_TRY(hipGetLastError());
@@ -3679,14 +3720,95 @@ int32_t rt_query_occluded(rt_scene* s, int32_t slot, int64_t n, const rt_ray_bat
                           const rt_query_bounds* declared, uint32_t flags, void* stream) {
     return query_impl(s, slot, n, rays, nullptr, out, true, declared, flags, stream);
 }
+int32_t rt_query_closest_masked(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, const rt_hit_batch* hits,
+                                const rt_query_bounds* declared, uint32_t flags, void* stream, const rt_ray_masks* masks) {
+    return query_impl(s, slot, n, rays, hits, nullptr, false, declared, flags, stream, masks);
+}
+int32_t rt_query_occluded_masked(rt_scene* s, int32_t slot, int64_t n, const rt_ray_batch* rays, uint8_t* out,
+                                 const rt_query_bounds* declared, uint32_t flags, void* stream, const rt_ray_masks* masks) {
+    return query_impl(s, slot, n, rays, nullptr, out, true, declared, flags, stream, masks);
+}
+
+// ---- ray masks (rtcore.h "ray masks"): the scene's instance-mask table ----------------
+// Host-side plus one copy per replica, under the scene's lock; no part of a commit.  The first call
+// allocates the table on every replica before any is written, so a refusal changes nothing.
+int32_t rt_scene_set_instance_masks(rt_scene* s, int32_t first, int32_t count, const uint32_t* masks) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (const int32_t rc = scene_lost(s)) return rc;
+    const int64_t n = (int64_t)s->host.insts.size();
+    if (first < 0 || count < 0 || (int64_t)first + count > n) return fail(RT_ERR_INVALID_ARG, "bad instance index or range");
+    if (count > 0 && !masks) return fail(RT_ERR_INVALID_ARG, "masks is NULL");
+    try {
+        std::lock_guard<std::mutex> lock(s->mu);
+        const bool fresh = s->inst_masks.empty();
+        std::vector<uint32_t> next = s->inst_masks;
+        if (fresh) next.assign((size_t)std::max<int64_t>(1, n), 0xffffffffu);
+        for (int32_t k = 0; k < count; ++k) next[(size_t)(first + k)] = masks[k];
+        // one replica's copy of table entries [a, a + m) from `src`
+        const auto put = [&](DeviceReplica& r, uint32_t* table, const std::vector<uint32_t>& src, size_t a, size_t m) {
+            hipError_t e = hipSetDevice(r.device);
+            if (e == hipSuccess) e = hipMemcpy(table + a, src.data() + a, m * 4, hipMemcpyHostToDevice);
+            if (e != hipSuccess) (void)hipGetLastError();
+            return e;
+        };
+        if (fresh) {
+            std::vector<uint32_t*> got;
+            const auto drop = [&]() {
+                for (size_t k = 0; k < got.size(); ++k) { (void)hipSetDevice(s->devs[k].device); (void)hipFree(got[k]); }
+            };
+            for (DeviceReplica& r : s->devs) {
+                uint32_t* p = nullptr;
+                if (hipSetDevice(r.device) != hipSuccess || hipMalloc((void**)&p, next.size() * 4) != hipSuccess) {
+                    (void)hipGetLastError();
+                    drop();
+                    return fail(RT_ERR_OOM, "the instance-mask table does not fit on the device");
+                }
+                got.push_back(p);
+            }
+            for (size_t k = 0; k < got.size(); ++k) {     // published below, once every table holds the masks
+                const hipError_t e = put(s->devs[k], got[k], next, 0, next.size());
+                if (e != hipSuccess) {
+                    drop();
+                    return fail(RT_ERR_DEVICE, hipGetErrorString(e));
+                }
+            }
+            for (size_t k = 0; k < got.size(); ++k) {
+                s->devs[k].inst_masks = got[k];
+                s->devs[k].bytes += (int64_t)next.size() * 4;
+            }
+        } else if (count > 0) {
+            for (size_t k = 0; k < s->devs.size(); ++k) {
+                const hipError_t e = put(s->devs[k], s->devs[k].inst_masks, next, (size_t)first, (size_t)count);
+                if (e != hipSuccess) {    // the replicas written so far get their old masks back: nothing changed
+                    for (size_t q = 0; q <= k; ++q)
+                        (void)put(s->devs[q], s->devs[q].inst_masks, s->inst_masks, (size_t)first, (size_t)count);
+                    return fail(RT_ERR_DEVICE, hipGetErrorString(e));
+                }
+            }
+        }
+        s->inst_masks.swap(next);
+        return RT_OK;
+    } catch (const std::bad_alloc&) {
+        return fail(RT_ERR_OOM, "host allocation failed");
+    }
+}
+int32_t rt_scene_instance_mask(const rt_scene* s, int32_t instance, uint32_t* mask) {
+    if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
+    if (!mask) return fail(RT_ERR_INVALID_ARG, "mask is NULL");
+    std::lock_guard<std::mutex> lock(const_cast<rt_scene*>(s)->mu);
+    if (instance < 0 || instance >= (int32_t)s->host.insts.size()) return fail(RT_ERR_INVALID_ARG, "bad instance index");
+    *mask = s->inst_masks.empty() ? 0xffffffffu : s->inst_masks[(size_t)instance];
+    return RT_OK;
+}
 
 // ---- first-hit buffers (rtcore.h "first-hit buffers"; gbuffer.h) -----------------------
 // The constants are the render's of that camera (make_params), so nothing is reduced and nothing is
 // read back: a device call only enqueues.  A host-array call is staged through the slot's query
 // scratch (query_stage: the ray in o / d / tlim / time, the record in the rest) in passes of at most
 // query_batch pixels of the packed selection, each pass copied out before the next reuses the staging.
-int32_t rt_render_gbuffer(rt_scene* s, int32_t slot, int32_t cam, int32_t first, int32_t step, const rt_gbuffer* out,
-                          uint32_t flags, void* stream_) {
+// mask != NULL: rt_render_gbuffer_masked (one ray mask for the call, the k_gbuffer_masked kernels)
+static int32_t gbuffer_impl(rt_scene* s, int32_t slot, int32_t cam, int32_t first, int32_t step, const rt_gbuffer* out,
+                            uint32_t flags, void* stream_, const uint32_t* mask) {
     if (!s) return fail(RT_ERR_NO_SCENE, "No scene loaded.");
     if (const int32_t rc = scene_lost(s)) return rc;
     const HostScene& S = s->host;
@@ -3713,6 +3835,8 @@ int32_t rt_render_gbuffer(rt_scene* s, int32_t slot, int32_t cam, int32_t first,
     int64_t batch = 0, n = 0;
     int walk = 0;
     bool tiles = false;
+    dev::QueryMasks K{};
+    K.all = mask ? *mask : 0xffffffffu;
     {   // prepared under the scene's lock: the render's constants of this camera, the slot's query scratch
         std::lock_guard<std::mutex> lock(s->mu);
         HIP_TRY(hipSetDevice(r.device));
@@ -3725,6 +3849,7 @@ int32_t rt_render_gbuffer(rt_scene* s, int32_t slot, int32_t cam, int32_t first,
         tiles = s->opt[kOptGBufferTiles] != 0;
         if (const int32_t rc = query_scratch(S, r, H.ids != nullptr, on_dev ? 0 : std::min(n, batch))) return rc;
         walk = select_walk(s, P, false);      // the render kernels' walk
+        K.table = r.inst_masks;
         const rt_camera& c = S.cams[cam];
         const double ce[3] = {c.position.x, c.position.y, c.position.z}, lens = std::fabs(c.aperture_size);
         r.q_last = rt_query_counts{};
@@ -3742,7 +3867,9 @@ int32_t rt_render_gbuffer(rt_scene* s, int32_t slot, int32_t cam, int32_t first,
     dev::GBufferBatch G{};
     G.centre = (flags & RT_GBUFFER_PIXEL_CENTRE) ? 1u : 0u;
     const size_t lds = (size_t)dev::kLds * kRenderBlock * sizeof(unsigned long long);
-#define MYRT_GBUF(W_) hipLaunchKernelGGL((dev::k_gbuffer<W_>), grid, dim3(kRenderBlock), lds, stream, P, B, G)
+#define MYRT_GBUF_(W_) hipLaunchKernelGGL((dev::k_gbuffer<W_>), grid, dim3(kRenderBlock), lds, stream, P, B, G)
+#define MYRT_GBUFM(W_) hipLaunchKernelGGL((dev::k_gbuffer_masked<W_>), grid, dim3(kRenderBlock), lds, stream, P, B, G, K)
+#define MYRT_GBUF(W_) do { if (mask) MYRT_GBUFM(W_); else MYRT_GBUF_(W_); } while (0)
     auto launch_rays = [&]() {
         const dim3 grid((unsigned)((G.n + dev::kGBufferRaysBlock - 1) / dev::kGBufferRaysBlock));
         hipLaunchKernelGGL(dev::k_gbuffer_rays, grid, dim3(dev::kGBufferRaysBlock), 0, stream, P, G);
@@ -3802,7 +3929,17 @@ int32_t rt_render_gbuffer(rt_scene* s, int32_t slot, int32_t cam, int32_t first,
         HIP_TRY(hipStreamSynchronize(stream));
     }
 #undef MYRT_GBUF
+#undef MYRT_GBUFM
+#undef MYRT_GBUF_
     return RT_OK;
+}
+int32_t rt_render_gbuffer(rt_scene* s, int32_t slot, int32_t cam, int32_t first, int32_t step, const rt_gbuffer* out,
+                          uint32_t flags, void* stream) {
+    return gbuffer_impl(s, slot, cam, first, step, out, flags, stream, nullptr);
+}
+int32_t rt_render_gbuffer_masked(rt_scene* s, int32_t slot, int32_t cam, int32_t first, int32_t step,
+                                 const rt_gbuffer* out, uint32_t flags, void* stream, uint32_t mask) {
+    return gbuffer_impl(s, slot, cam, first, step, out, flags, stream, &mask);
 }
 #undef MYRT_BY_WALK
 

@@ -270,6 +270,12 @@ struct TwParked {
 // slot encoding of refit.h (kHiddenNear) and the NaN tbox only keep rays from getting that far.
 // A rebuilt tree holds the visible pairs only; set_wide withholds it (tw_walk instead) whenever a
 // visible pair is missing from it.
+// Masked-out instances (rtcore.h "ray masks") need no new term either: for a ray
+// with mask m, an instance whose mask shares no bit with m is an instance the reference scene of
+// that ray (engine masked_scene) does not hold.  Every walk skips it where it would enter it - a
+// pair here, a leaf run of the identity tree, a marker of tw_walk and ut_walk, a TLAS leaf entry of
+// the binary walks - and the trees stay superset filters of what remains; the re-walks of equal-t
+// ties and out-of-range rays carry the same mask, so a tie cannot bring the instance back.
 __device__ __forceinline__ bool fit_boxes_exact(const RenderParams& P, int k, int t0, const V3& o, const V3& d,
                                                 const V3& ol, const V3& dl) {
     const DWideInst& WI = P.winst[k];
@@ -322,9 +328,10 @@ __device__ __forceinline__ void fit_local(const RenderParams& P, int k, const V3
 // its leaves keeps its pruning limit high.  Removed; git history keeps it.)
 // W: the ray, kept by the caller (TwWorld) or parked (fit walks of the megakernels: the world ray
 // is read back at a pair, where its local ray is formed, and not live across the walk).
-template <bool COUNT, bool SHADOW, bool FIT = false, class World = TwWorld>
+// M: the ray's mask (device.h NoMask / RayMask), asked once per pair (FIT) or leaf run.
+template <bool COUNT, bool SHADOW, bool FIT = false, class World = TwWorld, class M = NoMask>
 __device__ __forceinline__ bool wide_walk(const RenderParams& P, const World& W, const V3& inv, double tlo,
-                                          double tmax, Hit& h, bool& tie, Stack& st, Counts& c) {
+                                          double tmax, Hit& h, bool& tie, Stack& st, Counts& c, const M& mk = M{}) {
     const WRay R = wide_ray(P, W.o(), inv, P.wdelta);
     const double eps = P.eps;
     float lim = SHADOW ? wide_limit(P, tmax) : 3.0e38f;
@@ -346,6 +353,7 @@ __device__ __forceinline__ bool wide_walk(const RenderParams& P, const World& W,
             const DFitPair pr = P.fpairs[x];
             t0 = pr.t0;
             k = pr.inst;
+            if (!mk.pass(k)) return false;                 // ahead of fit_local: the cached local ray stays
             if (kCache) {
                 if (k != ck) {
                     fit_local(P, k, W.o(), W.d(), cro, crd);
@@ -365,6 +373,8 @@ __device__ __forceinline__ bool wide_walk(const RenderParams& P, const World& W,
             return FIT ? fit_boxes_exact(P, k, t0, W.o(), W.d(), ro, rd) : leaf_box_exact(P, t0, ro, rd);
         };
         auto run = [&](const auto* tris) {
+            // identity tree: a run belongs to one instance, its records' `prim`
+            if (!FIT && !mk.pass(tris[t0].prim)) return false;
             for (int t = t0;; ++t) {
                 const auto T = tris[t];                    // by value: `last` arrives with the vertices
                 if (COUNT) c.tris++;
@@ -437,9 +447,9 @@ __device__ __forceinline__ bool wide_walk(const RenderParams& P, const World& W,
 __device__ __forceinline__ bool tw_is_tlas(const RenderParams& P, int ref) {
     return ref >= 0 ? ref < P.tw_tlas_nodes : ~ref >= P.ut_marker_base;
 }
-template <bool SHADOW, class World>
+template <bool SHADOW, class World, class M = NoMask>
 __device__ __forceinline__ bool tw_walk(const RenderParams& P, const World& W, double tlo, double tmax,
-                                        Hit& h, bool& tie, bool& redo, Stack& st) {
+                                        Hit& h, bool& tie, bool& redo, Stack& st, const M& mk = M{}) {
     const double eps = P.eps;
     WRay R;
     {
@@ -466,7 +476,8 @@ __device__ __forceinline__ bool tw_walk(const RenderParams& P, const World& W, d
             const V3 o = W.o(), d = W.d();
             const V3 inv = rcp(d);
             double dt;
-            if (slab_hit<true>(WI.tbox[0], WI.tbox[1], WI.tbox[2], WI.tbox[3], WI.tbox[4], WI.tbox[5], o, inv, eps, dt) &&
+            if (mk.pass(k) &&
+                slab_hit<true>(WI.tbox[0], WI.tbox[1], WI.tbox[2], WI.tbox[3], WI.tbox[4], WI.tbox[5], o, inv, eps, dt) &&
                 !(dt > limd)) {
                 const DInstance& I = P.insts[k];
                 const V3 ol2 = m4_point(I.w2l, o, 1.0), dl2 = m4_point(I.w2l, d, 0.0);

@@ -311,6 +311,54 @@ class RayTracerEngine:
         return visible_subset(self.scene, [self.instance_of(i) >= 0 and self.is_visible(i)
                                            for i in range(len(self.scene.objects))])
 
+    # -- ray masks (rtcore.h "ray masks")
+    def set_mask(self, object_index: int, mask: int):
+        """Give the instance of scene object `object_index` the 32 mask bits `mask`
+        (rt_scene_set_instance_masks): applied at once, no commit, on static scenes too.  A masked
+        query's ray sees the instance iff the two masks share a bit and the instance is visible."""
+        self.set_mask_many([object_index], [mask])
+
+    def set_mask_many(self, object_indices, masks):
+        """set_mask for several objects: `masks` is one value for all, or one per object.  Objects
+        whose instances are consecutive go down in one rt_scene_set_instance_masks call."""
+        objs = [int(o) for o in object_indices]
+        vals = [int(masks)] * len(objs) if isinstance(masks, (int, np.integer)) else [int(m) for m in masks]
+        if len(vals) != len(objs):
+            raise ValueError("one mask per object")
+        if any(m < 0 or m > 0xFFFFFFFF for m in vals):
+            raise ValueError("a mask is 32 bits")
+        inst = [self.instance_of(o) for o in objs]
+        for o, k in zip(objs, inst):
+            if k < 0:
+                raise RenderError(A.RT_ERR_INVALID_ARG, f"object {o} produced no instance")
+        lib, q = load_library(), 0
+        while q < len(inst):
+            e = q + 1
+            while e < len(inst) and inst[e] == inst[e - 1] + 1:
+                e += 1
+            buf = (C.c_uint32 * (e - q))(*vals[q:e])
+            _check(lib.rt_scene_set_instance_masks(self._h, inst[q], e - q, buf))
+            q = e
+
+    def mask_of(self, object_index: int) -> int:
+        """The mask of the instance of scene object `object_index` (0xFFFFFFFF until it was set)."""
+        k = self.instance_of(object_index)
+        if k < 0:
+            raise RenderError(A.RT_ERR_INVALID_ARG, f"object {object_index} produced no instance")
+        m = C.c_uint32(0)
+        _check(load_library().rt_scene_instance_mask(self._h, k, C.byref(m)))
+        return int(m.value)
+
+    def masked_scene(self, mask: int) -> Scene:
+        """A Scene holding only the objects a ray with mask `mask` sees: those whose instance is
+        visible as of the last commit() and whose mask shares a bit with `mask`, in scene order
+        (visible_subset).  oracle.OracleScene(eng.masked_scene(m)) is the reference of a masked query."""
+        keep = []
+        for i in range(len(self.scene.objects)):
+            k = self.instance_of(i)
+            keep.append(k >= 0 and (not self.dynamic or self.is_visible(i)) and (self.mask_of(i) & int(mask)) != 0)
+        return visible_subset(self.scene, keep)
+
     # -- deforming meshes (BVHBuilder.refit applied to a BLAS, BVH.swift:254-291)
     def vertex_count(self, object_index: int) -> int:
         """The vertex count of mesh object `object_index` (rt_scene_mesh_vertex_count)."""
@@ -615,7 +663,7 @@ class RayTracerEngine:
 
     # -- ray queries (rt_query_closest / rt_query_occluded)
     def query_closest(self, origins, dirs, tmin=None, time=None, *, slot: int = 0, want=("t", "uv", "ids"),
-                      bounds=None) -> "RayHits":
+                      bounds=None, mask=None) -> "RayHits":
         """Closest hits of caller-given rays through the scene's production walks (rt_query_closest).
         `origins` / `dirs` are (N, 3) float64: numpy arrays in give numpy arrays out; contiguous
         float64 torch tensors on the slot's device are used in place, the work is enqueued on
@@ -623,7 +671,10 @@ class RayTracerEngine:
         synchronises).  `tmin` / `time` are per-ray arrays of the same kind, or None (0).
         `want` names the RayHits fields to fill: t, uv, ids, point, normal, flags.
         `bounds` = (origin_reach, origin_coord, dir_norm) declares the batch's maxima (rays beyond
-        them come back flagged RT_HIT_OUT_OF_BOUNDS, untraced); None lets the device find them."""
+        them come back flagged RT_HIT_OUT_OF_BOUNDS, untraced); None lets the device find them.
+        `mask`: None is the unmasked query (instance masks are ignored); an int gives every ray
+        that mask; a uint32 numpy array - with device rays a torch int32 / uint32 tensor on their
+        device, whose bits are the masks - gives ray i mask[i] (rt_query_closest_masked, set_mask)."""
         unknown = set(want) - set(RayHits.FIELDS)
         if unknown:
             raise ValueError(f"unknown RayHits fields {sorted(unknown)}")
@@ -636,18 +687,30 @@ class RayTracerEngine:
                 a = alloc((n, cols) if cols > 1 else (n,), dt)
                 setattr(hits, name, a)
                 setattr(hb, name, _ptr(a))
-        _check(load_library().rt_query_closest(self._h, int(slot), n, C.byref(rays), C.byref(hb), _bounds(bounds),
-                                               A.RT_QUERY_DEVICE if on_dev else 0, _stream(on_dev)))
+        if mask is None:
+            _check(load_library().rt_query_closest(self._h, int(slot), n, C.byref(rays), C.byref(hb), _bounds(bounds),
+                                                   A.RT_QUERY_DEVICE if on_dev else 0, _stream(on_dev)))
+        else:
+            rm, keep_mask = _ray_masks(mask, n, on_dev, origins)
+            _check(load_library().rt_query_closest_masked(self._h, int(slot), n, C.byref(rays), C.byref(hb),
+                                                          _bounds(bounds), A.RT_QUERY_DEVICE if on_dev else 0,
+                                                          _stream(on_dev), C.byref(rm)))
         return hits
 
-    def query_occluded(self, origins, dirs, tmax=None, time=None, *, slot: int = 0, bounds=None):
+    def query_occluded(self, origins, dirs, tmax=None, time=None, *, slot: int = 0, bounds=None, mask=None):
         """Any hit of caller-given segments (rt_query_occluded): per ray 0 = free, 1 = blocked, 2 = not
         traced (beyond the declared `bounds`, or non-finite), as a uint8 numpy array or torch tensor;
-        arguments as query_closest (`tmax` None = +inf)."""
+        arguments as query_closest (`tmax` None = +inf; `mask`: rt_query_occluded_masked)."""
         rays, n, on_dev, keep, alloc = _query_rays(origins, dirs, tmax, time)    # keep: as in query_closest
         out = alloc((n,), np.uint8)
-        _check(load_library().rt_query_occluded(self._h, int(slot), n, C.byref(rays), C.c_void_p(_ptr(out)),
-                                                _bounds(bounds), A.RT_QUERY_DEVICE if on_dev else 0, _stream(on_dev)))
+        if mask is None:
+            _check(load_library().rt_query_occluded(self._h, int(slot), n, C.byref(rays), C.c_void_p(_ptr(out)),
+                                                    _bounds(bounds), A.RT_QUERY_DEVICE if on_dev else 0, _stream(on_dev)))
+        else:
+            rm, keep_mask = _ray_masks(mask, n, on_dev, origins)
+            _check(load_library().rt_query_occluded_masked(self._h, int(slot), n, C.byref(rays), C.c_void_p(_ptr(out)),
+                                                           _bounds(bounds), A.RT_QUERY_DEVICE if on_dev else 0,
+                                                           _stream(on_dev), C.byref(rm)))
         return out
 
     def last_query_stats(self, slot: int = 0) -> A.rt_query_counts:
@@ -671,6 +734,18 @@ class RayTracerEngine:
         numpy arrays come back by default.  `out` = a dict, keyed as `want`, of contiguous float64 /
         int32 / uint8 torch tensors on the slot's device: they are written in place, enqueued on
         torch.cuda.current_stream() with no synchronisation, and `want` is ignored."""
+        return self._first_hits(None, camera_index, chunk_first, chunk_step, want, centre, frame_layout, slot, out)
+
+    def first_hits_masked(self, mask: int, camera_index: int = 0, chunk_first: int = 0, chunk_step: int = 1, *,
+                          want=("rays", "t", "ids"), centre: bool = False, frame_layout: bool = False, slot: int = 0,
+                          out=None) -> "FirstHits":
+        """first_hits with one ray mask for the whole call (rt_render_gbuffer_masked): a camera layer,
+        picking against selectable objects.  The record is query_closest(exported rays, mask=mask)'s."""
+        if not 0 <= int(mask) <= 0xFFFFFFFF:
+            raise ValueError("a mask is 32 bits")
+        return self._first_hits(int(mask), camera_index, chunk_first, chunk_step, want, centre, frame_layout, slot, out)
+
+    def _first_hits(self, mask, camera_index, chunk_first, chunk_step, want, centre, frame_layout, slot, out):
         cam = self.scene.cameras[camera_index] if 0 <= camera_index < len(self.scene.cameras) else None
         W, H = (max(1, int(cam.image_resolution[0])), max(1, int(cam.image_resolution[1]))) if cam else (0, 0)
         rows = H if frame_layout else rows_for_chunks(H, chunk_first, chunk_step)
@@ -698,8 +773,12 @@ class RayTracerEngine:
             setattr(gb if ray else gb.hits, FirstHits.ABI.get(name, name), _ptr(a))
         flags = (A.RT_GBUFFER_DEVICE if on_dev else 0) | (A.RT_GBUFFER_PIXEL_CENTRE if centre else 0) | \
                 (A.RT_GBUFFER_FRAME_LAYOUT if frame_layout else 0)
-        _check(load_library().rt_render_gbuffer(self._h, int(slot), int(camera_index), int(chunk_first),
-                                                int(chunk_step), C.byref(gb), flags, _stream(on_dev)))
+        if mask is None:
+            _check(load_library().rt_render_gbuffer(self._h, int(slot), int(camera_index), int(chunk_first),
+                                                    int(chunk_step), C.byref(gb), flags, _stream(on_dev)))
+        else:
+            _check(load_library().rt_render_gbuffer_masked(self._h, int(slot), int(camera_index), int(chunk_first),
+                                                           int(chunk_step), C.byref(gb), flags, _stream(on_dev), mask))
         return res
 
     def bvh_hash(self, instance: int) -> int:
@@ -873,6 +952,31 @@ def _query_rays(origins, dirs, tlim, time):
             return np.empty(shape, dtype)
     rays.origin, rays.dir, rays.tlimit, rays.time = (_ptr(a) for a in keep)
     return rays, n, on_dev, keep, alloc
+
+
+def _ray_masks(mask, n: int, on_dev: bool, origins):
+    """rt_ray_masks for a query of n rays: (the struct, the array it points into)."""
+    rm = A.rt_ray_masks()
+    if isinstance(mask, (int, np.integer)):
+        if not 0 <= int(mask) <= 0xFFFFFFFF:
+            raise ValueError("a mask is 32 bits")
+        rm.per_ray, rm.all = None, int(mask)
+        return rm, None
+    if on_dev:
+        import torch
+        ok = (torch.int32, getattr(torch, "uint32", torch.int32))
+        if not isinstance(mask, torch.Tensor) or mask.device != origins.device or mask.dtype not in ok or \
+                not mask.is_contiguous() or mask.numel() != n:
+            raise ValueError(f"mask: an int, or a contiguous int32 / uint32 tensor of {n} on {origins.device}")
+        keep = mask
+    else:
+        keep = np.ascontiguousarray(mask.numpy() if hasattr(mask, "data_ptr") else mask)
+        if keep.dtype == np.int32:
+            keep = keep.view(np.uint32)
+        if keep.dtype != np.uint32 or keep.size != n:
+            raise ValueError(f"mask: an int, or a uint32 array of {n}")
+    rm.per_ray, rm.all = _ptr(keep), 0
+    return rm, keep
 
 
 def query_tables(scene: Scene, flags: int = 0) -> dict:
